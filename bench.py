@@ -7,10 +7,12 @@ arithmetic (np.fft / np.convolve on complex128, modulation/models.py:32,46-48). 
 complete Simulation-run of the hot path over `--symbols` OFDM symbols per GPU (TX kernel, power
 exchange, RX kernel, counter reduction, counts on the host).  Default 10 steps x 1e6 symbols =
 the "1e7 symbols at one SNR" of config (b).  `value` is measured after exactly `--warmup`
-untimed steps; the same path in complex64 is reported beside it (`c64_variant`), and so is a
-second complex128 measurement after a clock-ramp warmup (`value_after_ramp`).  Rank 0 also
+untimed steps.  A plain run does no more than that: set-up, warmup, the K timed steps, the
+result line (and `--dump-outputs DIR`: what the last timed step returned, as DIR/<field>.npy).
+With `--full` the same path in complex64 is reported beside it (`c64_variant`), and so is a
+second complex128 measurement after a clock-ramp warmup (`value_after_ramp`); rank 0 also
 reports the BER Delta dB of the timed run against the reference-stream path (the second half of
-the BASELINE metric) and the CPU baseline.
+the BASELINE metric) and the CPU baseline, and a `--sweep` adds its per-kernel roofline step.
 
 Multi-GPU: `--gpus N` without a torch.distributed environment re-launches this script as N
 ranks (torch.distributed.run, one process per GPU, before anything touches a GPU); each rank
@@ -384,11 +386,24 @@ def timed_steps(rt: Runtime, engine, total: int, snr: float, steps: int, seed0: 
     t0 = time.perf_counter()
     pending = engine.run_pipelined(total, snr, range(seed0, seed0 + steps), group=rt.group, events=events,
                                    lanes=lanes)
-    bit_errors = sum(p.result().bit_errors for p in pending)
+    results = [p.result() for p in pending]
     rt.sync()
     rt.barrier()
     rt.sync()
-    return rt.max_over_ranks(time.perf_counter() - t0), bit_errors
+    return rt.max_over_ranks(time.perf_counter() - t0), results
+
+
+# what a caller of the timed path receives per run (engine.LinkStats), as --dump-outputs writes it
+OUTPUT_FIELDS = ("bit_errors", "symbol_errors", "power_sum", "x_power_sum", "x_peak", "papr_db")
+
+
+def dump_outputs(path: str, runs) -> None:
+    """--dump-outputs: the LinkStats of the last timed step's runs (one run, or one per point of a
+    sweep, in point order) as `path`/<field>.npy, one float64 per run (the counts are exact in
+    float64).  The seeds of the timed steps are fixed, so the same arguments give the same inputs."""
+    os.makedirs(path, exist_ok=True)
+    for name in OUTPUT_FIELDS:
+        np.save(os.path.join(path, name + ".npy"), np.array([getattr(r, name) for r in runs], dtype=np.float64))
 
 
 def roofline(events, N: int, bps: int, cp: int, w: int, traffic, issue=None):
@@ -446,7 +461,8 @@ def measure(rt: Runtime, args, cfg, precision: str, per_gpu: int, factory, ramp:
     for i in range(args.warmup):
         engine.run(total, snr, seed=10_000 + i, group=rt.group)
     events = None if rt.cpu else []
-    elapsed, bit_errors = timed_steps(rt, engine, total, snr, args.steps, 0, events, lanes)
+    elapsed, results = timed_steps(rt, engine, total, snr, args.steps, 0, events, lanes)
+    bit_errors = sum(r.bit_errors for r in results)
     w = PRECISIONS[precision][1]
     key = args.config if precision == "f32" else f"{args.config}_{precision}"
     rec = {
@@ -457,6 +473,7 @@ def measure(rt: Runtime, args, cfg, precision: str, per_gpu: int, factory, ramp:
                              None if rt.cpu else pmc_issue(key)),
         "ber": bit_errors / (engine.valid_bits(total) * args.steps),
         "bits": engine.valid_bits(total) * args.steps,
+        "last_step": results[-1:],
     }
     rec["path_hbm_fraction"] = rec["value"] * 2 * kernel_bytes_per_symbol(N, bps, cp, w) / (
         HBM_PEAK_GBS * 1e9 * rt.world)
@@ -563,7 +580,8 @@ def measure_sweep(rt: Runtime, args, groups, precision: str, per_gpu: int, facto
         pend.append(eng.run_pipelined(total, snrs * args.steps,
                                       [1_000_000 * gi + 1000 * st + k for st in range(args.steps)
                                        for k in range(len(snrs))], group=rt.group, lanes=lanes))
-    errs = [[p.result().bit_errors for p in ps] for ps in pend]
+    results = [[p.result() for p in ps] for ps in pend]
+    errs = [[r.bit_errors for r in rs] for rs in results]
     rt.sync()
     rt.barrier()
     rt.sync()
@@ -576,12 +594,12 @@ def measure_sweep(rt: Runtime, args, groups, precision: str, per_gpu: int, facto
             e = sum(errs[gi][k::len(snrs)])
             points.append({"snr_db": q, "qam_order": gcfg[1] if gcfg[1] else "adaptive", "bits_per_ofdm_symbol": eng.bps,
                            "ber": e / nbits, "bits": nbits})
-    # the kernels' launch times for the roofline: one more sweep step after the timed region, on ONE
-    # lane with HIP events around every launch -- on two lanes a kernel's events would also span the
+    # --full: the kernels' launch times for the roofline: one more sweep step after the timed region, on
+    # ONE lane with HIP events around every launch -- on two lanes a kernel's events would also span the
     # other lane's overlapping kernel (round 4's sweep line reported that bound, not a measurement);
     # the group whose symbols carry the most bits stands for the sweep
     roof = None
-    if not rt.cpu:
+    if args.full and not rt.cpu:
         gi = max(range(len(engines)), key=lambda j: engines[j].bps)
         events = []
         for p in engines[gi].run_pipelined(total, groups[gi][1], [90_000 + k for k in range(len(groups[gi][1]))],
@@ -597,6 +615,8 @@ def measure_sweep(rt: Runtime, args, groups, precision: str, per_gpu: int, facto
         "dtype": PRECISIONS[precision][0],
         "lanes": lanes,
         "roofline": roof,
+        # the last timed step's runs, in point order
+        "last_step": [r for (_, snrs), rs in zip(groups, results) for r in rs[len(rs) - len(snrs):]],
         "sweep": {"snr_db": [pt["snr_db"] for pt in points], "ber": [pt["ber"] for pt in points],
                   # one value when every group's symbols carry the same bits, else one per group (in
                   # group order; per_point[*].bits holds every point's own)
@@ -641,7 +661,16 @@ def main():
                          "profiles/r06p_sweep_lanes_c.txt)")
     ap.add_argument("--ref-symbols", type=int, default=12000,
                     help="--sweep: reference-stream OFDM symbols per point near the BER 1e-4 crossing (26..29 dB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the other precision's companion run, the "
+                         "value_after_ramp measurement, the BER check against the reference streams, the CPU "
+                         "baseline and a sweep's per-kernel roofline step (each still has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (its run's LinkStats "
+                         "fields; one entry per point with --sweep) as DIR/<field>.npy in float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.config is None:
         args.config = "c" if args.sweep else "b"
 
@@ -662,9 +691,11 @@ def main():
         return sweep_main(rt, args, cfg, factory)
     per_gpu = args.symbols if args.symbols else 1_000_000 // max(1, N // 1024)
     total = per_gpu * rt.world
-    engine, head = measure(rt, args, cfg, args.precision, per_gpu, factory, ramp=True)
+    engine, head = measure(rt, args, cfg, args.precision, per_gpu, factory, ramp=args.full)
+    if args.dump_outputs and rt.rank == 0:
+        dump_outputs(args.dump_outputs, head["last_step"])
     variant = None
-    if not args.no_variant:
+    if args.full and not args.no_variant:
         other = "f32" if args.precision == "f64" else "f64"
         _, variant = measure(rt, args, cfg, other, per_gpu, factory, ramp=False)
     devices = rt.gather(rt.dev if not rt.cpu else "cpu")
@@ -703,11 +734,11 @@ def main():
     if variant is not None:
         out[("c64" if variant["dtype"].startswith("c64") else "c128") + "_variant"] = {
             k: variant[k] for k in ("value", "ms_per_step", "dtype", "roofline", "path_hbm_fraction", "ber")}
-    if rt.rank == 0 and not args.no_ber_check and not rt.cpu:
+    if rt.rank == 0 and args.full and not args.no_ber_check and not rt.cpu:
         eng64 = make_engine(cfg, "f64")
         out["ber_vs_reference"] = ber_vs_reference(eng64, N, engine.cp, snr, head["ber"], head["bits"],
                                                    symbols=max(2000, 16000 * 1024 // N))
-    if rt.rank == 0 and not args.no_cpu_baseline:
+    if rt.rank == 0 and args.full and not args.no_cpu_baseline:
         # on rank 0 after every GPU measurement, for any number of ranks (the other ranks wait at
         # rt.finish()): the reference CPU path on the node's host cores, in the same run
         out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_sample or max(100, 30000 * 1024 // N))
@@ -727,6 +758,8 @@ def sweep_main(rt: Runtime, args, cfg, factory):
     groups = sweep_groups(args.config, cfg)
     per_gpu = args.symbols if args.symbols else 100_000 // max(1, N // 1024)
     engines, head = measure_sweep(rt, args, groups, args.precision, per_gpu, factory)
+    if args.dump_outputs and rt.rank == 0:
+        dump_outputs(args.dump_outputs, head["last_step"])
     engine = engines[0]
     total = per_gpu * rt.world
     devices = rt.gather(rt.dev if not rt.cpu else "cpu")
@@ -760,7 +793,7 @@ def sweep_main(rt: Runtime, args, cfg, factory):
     if args.config == "c" or (args.config not in ("d", "e") and M):
         c_phx = crossing(sw["snr_db"], sw["ber"])
         out["ber_1e-4_crossing_db"] = {"throughput": c_phx}
-        if rt.rank == 0 and not args.no_ber_check and not rt.cpu:
+        if rt.rank == 0 and args.full and not args.no_ber_check and not rt.cpu:
             near = [q for q in sw["snr_db"] if 26.0 <= q <= 29.0]
             eng64 = make_engine(cfg, "f64")
             ref = reference_sweep(eng64, N, engine.cp, near, max(1000, args.ref_symbols * 1024 // N))
@@ -775,7 +808,7 @@ def sweep_main(rt: Runtime, args, cfg, factory):
         # SER ~1e-3 at every SNR; 256-QAM stays above 1e-4 to 30 dB) -- the single-point bench lines
         # carry the BER check of these configs (ber_vs_reference)
         out["ber_1e-4_crossing_db"] = None
-    if rt.rank == 0 and not args.no_cpu_baseline:
+    if rt.rank == 0 and args.full and not args.no_cpu_baseline:
         cpu_cfg = (N, M, ch, ratio, eq_name, 27.75 if args.config == "c" else snr, desc)
         out["cpu_baseline"] = cpu_baseline(cpu_cfg, args.cpu_sample or max(100, 30000 * 1024 // N))
         if args.config == "e":

@@ -12,6 +12,19 @@ from conftest import ROOT
 import bench
 
 
+def _env():
+    """Environment of a bench.py child on the CPU engine double: the import paths, no inherited rank
+    variables and no visible GPU -- the double computes on CPU tensors, and on a box with a GPU every
+    rank would otherwise bind a device ordinal of its own."""
+    env = dict(os.environ)
+    env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"),
+                                         os.path.join(ROOT, "ofdm-based-systems_amd"), env.get("PYTHONPATH", "")])
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = ""
+    return env
+
+
 def test_algorithmic_bytes_match_the_survey():
     # SURVEY 8(d): B_alg = 2 ceil(bps / 8) + 2 (N + cp) 8 per symbol, split evenly over TX / RX;
     # worked values (b) 17 920 B, (c) 18 032 B, (e) 1024 b + 65 584 B at b = 8
@@ -55,13 +68,10 @@ def test_bench_gpus_flag_launches_ranks(gpus):
     import subprocess
     import sys
 
-    env = dict(os.environ)
-    env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"),
-                                         os.path.join(ROOT, "ofdm-based-systems_amd"), env.get("PYTHONPATH", "")])
-    env.pop("WORLD_SIZE", None)
+    env = _env()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--backend", "gloo",
                         "--engine-factory", "bench_double:make_engine", "--config", "b", "--symbols", "3",
-                        "--steps", "2", "--warmup", "1", "--cpu-sample", "2", "--no-ber-check", "--no-variant",
+                        "--steps", "2", "--warmup", "1", "--full", "--cpu-sample", "2", "--no-ber-check", "--no-variant",
                         "--ramp-seconds", "0"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -83,17 +93,13 @@ def test_bench_one_rank_under_torchrun_takes_the_process_group():
     import subprocess
     import sys
 
-    env = dict(os.environ)
-    env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"),
-                                         os.path.join(ROOT, "ofdm-based-systems_amd"), env.get("PYTHONPATH", "")])
-    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
-        env.pop(k, None)
+    env = _env()
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     args = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "gloo", "--engine-factory",
             "bench_double:make_engine", "--config", "b", "--symbols", "3", "--steps", "2", "--warmup", "1",
-            "--cpu-sample", "2", "--no-ber-check", "--no-variant", "--ramp-seconds", "0"]
+            "--full", "--cpu-sample", "2", "--no-ber-check", "--no-variant", "--ramp-seconds", "0"]
     lines = {}
     for name, cmd in (("torchrun", [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
                                     "--master-addr=127.0.0.1", f"--master-port={port}"] + args),
@@ -122,10 +128,7 @@ def test_bench_sweep_two_ranks():
     import subprocess
     import sys
 
-    env = dict(os.environ)
-    env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"),
-                                         os.path.join(ROOT, "ofdm-based-systems_amd"), env.get("PYTHONPATH", "")])
-    env.pop("WORLD_SIZE", None)
+    env = _env()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
                         "--engine-factory", "bench_double:make_engine", "--sweep", "--symbols", "1",
                         "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-ber-check"],
@@ -147,10 +150,7 @@ def test_bench_sweep_config_e_two_ranks():
     import subprocess
     import sys
 
-    env = dict(os.environ)
-    env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"),
-                                         os.path.join(ROOT, "ofdm-based-systems_amd"), env.get("PYTHONPATH", "")])
-    env.pop("WORLD_SIZE", None)
+    env = _env()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
                         "--engine-factory", "bench_double:make_engine", "--sweep", "--config", "e", "--symbols", "1",
                         "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-ber-check"],
@@ -171,10 +171,7 @@ def _bench(args, timeout=900):
     import subprocess
     import sys
 
-    env = dict(os.environ)
-    env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"),
-                                         os.path.join(ROOT, "ofdm-based-systems_amd"), env.get("PYTHONPATH", "")])
-    env.pop("WORLD_SIZE", None)
+    env = _env()
     env["OMP_NUM_THREADS"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--backend", "gloo",
                         "--engine-factory", "bench_double:make_engine", "--no-ber-check", "--ramp-seconds", "0"] + args,
@@ -192,7 +189,7 @@ def test_bench_eight_ranks_count_what_one_rank_counts(config, sweep):
     line, and with the same global symbols per point (8 ranks x 1 symbol against 1 rank x 8 -- the
     streams are per symbol, the power exchange exact) every point's BER equals the one-rank run's."""
     extra = ["--sweep"] if sweep else ["--no-variant"]
-    common = ["--config", config, "--steps", "1", "--warmup", "0", "--cpu-sample", "1"] + extra
+    common = ["--config", config, "--steps", "1", "--warmup", "0", "--full", "--cpu-sample", "1"] + extra
     d8 = _bench(["--gpus", "8", "--symbols", "1"] + common)
     d1 = _bench(["--gpus", "1", "--symbols", "8"] + common)
     npts = d8["sweep"]["points"] if sweep else 1
@@ -207,3 +204,34 @@ def test_bench_eight_ranks_count_what_one_rank_counts(config, sweep):
         assert [p["bits"] for p in d8["sweep"]["per_point"]] == [p["bits"] for p in d1["sweep"]["per_point"]]
     else:
         assert d8["ber"] == d1["ber"]
+
+
+def test_plain_run_is_lean_and_dumps_what_the_last_step_returned(tmp_path):
+    """A plain run carries the headline fields and none of the --full measurements; --dump-outputs
+    writes the last timed step's LinkStats fields as float64 .npy files, identical from run to run
+    (fixed seeds), and --steps sets which step is the last one."""
+    common = ["--gpus", "1", "--symbols", "4", "--config", "b", "--warmup", "0"]
+    d = _bench(common + ["--steps", "1", "--dump-outputs", str(tmp_path / "a")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "OFDM symbols/s"
+    for k in ("cpu_baseline", "c64_variant", "c128_variant", "value_after_ramp", "ber_vs_reference"):
+        assert k not in d, k
+    _bench(common + ["--steps", "1", "--dump-outputs", str(tmp_path / "b")])
+    _bench(common + ["--steps", "2", "--dump-outputs", str(tmp_path / "c")])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(f + ".npy" for f in bench.OUTPUT_FIELDS)
+    a, b, c = ({n: np.load(tmp_path / x / n) for n in names} for x in "abc")
+    for n in names:
+        assert a[n].dtype == np.float64 and a[n].shape == (1,) and np.array_equal(a[n], b[n]), n
+    assert a["bit_errors.npy"][0] == round(d["ber"] * 4 * 1024 * 6)
+    assert a["power_sum.npy"][0] > 0 and not np.array_equal(a["power_sum.npy"], c["power_sum.npy"])  # seed 0 / seed 1
+
+
+def test_sweep_dump_has_one_entry_per_point(tmp_path):
+    d = _bench(["--gpus", "1", "--symbols", "1", "--sweep", "--config", "e", "--steps", "2", "--warmup", "0",
+                "--dump-outputs", str(tmp_path)])
+    assert "cpu_baseline" not in d and d["sweep"]["points"] == 15
+    for f in bench.OUTPUT_FIELDS:
+        x = np.load(tmp_path / (f + ".npy"))
+        assert x.dtype == np.float64 and x.shape == (15,), f

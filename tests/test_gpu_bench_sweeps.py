@@ -20,7 +20,7 @@ def test_sweep_groups_count_what_single_runs_count(gpu, name):
     cfg = bench.CONFIGS[name]
     groups = bench.sweep_groups(name, cfg)
     per_gpu = 64
-    args = argparse.Namespace(lanes=2, warmup=0, steps=2)
+    args = argparse.Namespace(lanes=2, warmup=0, steps=2, full=True)  # --full: the roofline step of its own
     engines, rec = bench.measure_sweep(rt, args, groups, "f64", per_gpu, bench.make_engine)
     sw = rec["sweep"]
     assert sw["points"] == sum(len(q) for _, q in groups) == len(sw["per_point"])

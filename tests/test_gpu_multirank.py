@@ -86,7 +86,7 @@ def test_bench_one_rank_rccl_runs_the_node_path(gpu):
     max-over-ranks timing on RCCL, the device gather, the CPU baseline on rank 0 while the host
     group waits -- on the one GPU a box has.  The line reports its process group and the same BER as
     the plain one-process run over the same symbols."""
-    common = ["--gpus", "1", "--symbols", "100000", "--steps", "2", "--warmup", "1", "--no-ber-check",
+    common = ["--gpus", "1", "--symbols", "100000", "--steps", "2", "--warmup", "1", "--full", "--no-ber-check",
               "--no-variant", "--ramp-seconds", "0", "--cpu-sample", "100"]
     r = _launch([os.path.join(ROOT, "bench.py"), "--backend", "nccl"] + common, timeout=600, nproc=1)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -107,7 +107,7 @@ def test_bench_sweep_two_ranks_on_one_gpu(gpu, config):
     line): every point's BER equals the one-rank sweep's over the same global symbols (2 ranks x S
     against 1 rank x 2S), and the line carries n_gpus / devices of the two ranks."""
     per = {"c": 2000, "d": 1000, "e": 500}[config]
-    common = ["--sweep", "--config", config, "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+    common = ["--sweep", "--config", config, "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
               "--no-ber-check"]
     r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--symbols", str(per)] + common,
                 timeout=600)

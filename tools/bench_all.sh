@@ -5,7 +5,7 @@ export PYTHONUNBUFFERED=1
 tag=${1:-r02}
 mkdir -p gpurun_out
 for cfg in ${BENCH_CONFIGS:-b c d e}; do
-  timeout -k 10 240 python bench.py --config $cfg --steps ${BENCH_STEPS:-20} --warmup 5 \
+  timeout -k 10 240 python bench.py --full --config $cfg --steps ${BENCH_STEPS:-20} --warmup 5 \
       > gpurun_out/bench_${tag}_$cfg.json 2> gpurun_out/bench_${tag}_$cfg.err
   rc=$?; [ $rc -eq 0 ] || { echo "config $cfg rc=$rc"; tail -5 gpurun_out/bench_${tag}_$cfg.err; exit $rc; }
   python -c "import json; d=json.load(open('gpurun_out/bench_${tag}_$cfg.json')); print('$cfg', '%.4g sym/s'%d['value'], d['roofline']['avg_launch_ms'], 'frac %.3f'%d['roofline']['frac'], 'dB', d.get('ber_vs_reference',{}).get('delta_db'), 'cpu', d.get('cpu_baseline',{}).get('value'))"
