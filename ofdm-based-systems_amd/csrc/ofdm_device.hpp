@@ -258,6 +258,9 @@ __device__ __forceinline__ void static_for(F&& f) {
 }
 
 // ------------------------------------------------------------------ FFT geometry
+// elements of an LDS row of n padded by pad(): one pad slot per 16
+constexpr int padded_row(int n) { return n + (n >> 4); }
+
 template <int LOGN, int BLK = kBlock>
 struct Geo {
     static constexpr int N = 1 << LOGN;
@@ -265,8 +268,8 @@ struct Geo {
     static constexpr int E = 1 << LOGE;   // elements per thread
     static constexpr int TPS = N / E;     // threads per symbol
     static constexpr int SPB = BLK / TPS;  // symbols per workgroup
-    static constexpr int PADN = N + (N >> 4);  // padded LDS row (complex elements); with pad()
-                                                // conflict-free row spacing (tools/lds_banks.py)
+    static constexpr int PADN = padded_row(N);  // padded LDS row (complex elements); with pad()
+                                                 // conflict-free row spacing (tools/lds_banks.py)
 };
 
 __device__ __forceinline__ int pad(int i) { return i + (i >> 4); }

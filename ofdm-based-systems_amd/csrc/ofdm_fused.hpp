@@ -18,6 +18,7 @@
 // SC-OFDM / zero padding).
 #pragma once
 
+#include <algorithm>
 #include <type_traits>
 
 // Minimum waves per SIMD requested per fused kernel (register budget 512/waves), tuned on
@@ -206,54 +207,11 @@ constexpr bool tx_sep_lut() { return sizeof(R) == 8 && FB >= 2 && !(FB & 1) && L
 #ifndef OFDM_TX_BIG_WFIR_WAVES
 #define OFDM_TX_BIG_WFIR_WAVES 3
 #endif
-// LDS of the complex128 FIR TX at blk threads (upper estimate of its Carve sequence, smem_tx):
-// FIR rows -- window FIR: half a symbol's stream as complex samples, wfir_in(N/2 + 48) + 1 of
-// them (cp <= 32), or the FFT's N + N/16 reals if more; the run-time-tap FIR: fir_pad(N + 32) + 1
-// complex -- and the 7 complex tail samples per symbol, per-pass twiddles, the static LUT
-// (adaptive: the 512-entry pool and the per-subcarrier table), taps
-constexpr int f64_fir_lds(int fb, int logn, int blk, bool real_rows) {
-    const int n = 1 << logn, tps = logn < 4 ? 1 : n >> 4, spb = blk / tps;
-    const int fir = (n + 32) + ((n + 32) >> 4) + 1, half = 2 * (n / 2 + 48 + ((n / 2 + 48 + 7) >> 3) + 1);
-    const int padn = n + (n >> 4);
-    const int rows = spb * ((real_rows ? (half > padn ? half : padn) * 8 : fir * 16) + 7 * 16);
-    const int tt = tt_size(logn) * 16;
-    const int lut = fb == 1 ? (kMaxLut + 1) * 16 + 4 * n : (16 << fb);
-    return rows + tt + lut + 1024;
-}
-// static (__shared__) LDS of the fused kernels beside their dynamic rows (kLdsPerCu checks)
-template <typename R, int FB>
-constexpr size_t rx_static_lds() {
-    return 8 * kNoisePhases + (sizeof(R) == 8 && FB > 0 ? 16 * kNoisePhases : 16);
-}
-template <typename R, int FB, int LT>
-constexpr size_t tx_static_lds() {
-    const size_t lut = FB == 1 ? kMaxLut + 1 : (FB > 1 ? ((size_t)1 << FB) : 1);
-    const size_t sep = (sizeof(R) == 8 && FB >= 2 && !(FB & 1) && LT != 0) ? 2 * ((size_t)1 << (FB / 2)) : 1;
-    return lut * 2 * sizeof(R) + sep * sizeof(R);
-}
-// LT (throughput TX): 0 flat channel; 4 / 8 multipath with <= LT taps through the register
-// window FIR (N >= 256, cp <= TPS); -1 any multipath (run-time loop over taps).  ZPW: the complex128
-// window FIR with the zero-padding guard (and its run-time flat path for a one-tap channel) compiled
-// in; without it (cyclic prefix, L > 1: the bench configs) the kernel needs ~139 VGPRs instead of
-// 205-227 (3 waves per SIMD would fit with nothing spilled; measured no faster, DESIGN.md section 4)
-template <typename R, int FB, int LOGN, int LT, bool ZPW = false>
-constexpr int tx_block() {
-    if (sizeof(R) == 8 && FB > 0) {
-        if (LT == 0) return OFDM_F64_TX_BLOCK;
-        return f64_fir_lds(FB, LOGN, OFDM_F64_FIR_BLOCK, LT > 0) <= 160 * 1024 ? OFDM_F64_FIR_BLOCK : 256;
-    }
-    return FB > 0 && LOGN <= 10 ? (LT != 0 ? OFDM_TX_MP_BLOCK : OFDM_TX_FAST_BLOCK) : kBlock;
-}
-constexpr int block_waves(int blk, int dflt) { return blk >= 512 ? 4 : dflt; }
-template <typename R, int FB, int LOGN, int LT, bool ZPW = false>
-constexpr int tx_waves() {
-    if (sizeof(R) == 8 && FB > 0) {
-        if (LT == 0) return OFDM_F64_TX_WAVES;
-        return LOGN >= 12 ? OFDM_F64_FIR_WAVES_4K : OFDM_F64_FIR_WAVES;
-    }
-    if (FB > 0 && LT > 0 && LOGN > 10) return OFDM_TX_BIG_WFIR_WAVES;
-    return block_waves(tx_block<R, FB, LOGN, LT>(), FB > 0 && LT > 0 ? OFDM_TX_WFIR_WAVES : OFDM_TX_WAVES);
-}
+// LDS per CU on gfx950.  The complex128 FIR TX sizes its workgroup against it (tx_block), and a
+// throughput-kernel instantiation whose LDS would exceed it (a shape the plan allows but the
+// specialised layout cannot hold) runs the generic kernel instead of failing at launch
+// (tests/test_gpu_edges.py::test_lds_limit_shapes_run)
+constexpr size_t kLdsPerCu = 160 * 1024;
 // padded FIR row index of the throughput multipath TX: one slot per 16 elements
 __host__ __device__ constexpr int fir_pad(int i) { return i + (i >> 4); }
 // complex128 window-FIR TX, LDS slots (16 bytes) of the half-symbol row.  Stream phase: stream
@@ -558,6 +516,95 @@ template <typename R, int LOGN, int FB>
 constexpr bool uses_tt() { return FB > 0 && fast_tt<R, LOGN>(); }
 
 // ============================================================ fused TX
+// static (__shared__) LDS of k_tx beside its dynamic rows: the throughput kernels' LUT (2^FB
+// entries; adaptive: the pool + a zero entry) and its two axis tables (tx_sep_lut)
+template <int FB>
+constexpr int tx_lut_static() { return FB == 1 ? kMaxLut + 1 : (FB > 1 ? (1 << FB) : 1); }
+template <typename R, int FB, int LT>
+constexpr int tx_sep_static() { return tx_sep_lut<R, FB, LT>() ? 2 * (1 << (FB / 2)) : 1; }
+template <typename R, int FB, int LT>
+constexpr size_t tx_static_lds() { return tx_lut_static<FB>() * sizeof(cpx<R>) + tx_sep_static<R, FB, LT>() * sizeof(R); }
+// complex elements per symbol row: the plan's (tx_slot), or the window FIR's padded row if longer
+template <typename R, int LOGN, int FB, int LT>
+constexpr int tx_row_slot(int slot, int cp) {
+    if (!(FB > 0 && LT > 0)) return slot;
+    if (sizeof(R) == 8) {
+        // complex128: the row of reals carries half a symbol's stream as complex samples, half 0's
+        // m in [-(LT-1), cp + N/2) at wfir_in(A8 - cp + LT - 1 + m), and N / 2 transposed outputs
+        const int A8 = (cp + 7) & ~7;
+        slot = std::max(slot, 2 * (wfir_in(A8 + (1 << LOGN) / 2 + LT - 2, LT) + 1));
+        return std::max(slot, 2 * (wfir_out((1 << LOGN) / 2 - 1) + 1));
+    }
+    // window FIR row: stream samples [-(LT-1), N+cp) at fir_pad(R0 + m)
+    const int A = (cp + 15) & ~15, R0 = A - cp + LT - 1;
+    return std::max(slot, fir_pad(R0 + (1 << LOGN) + cp) + 1);
+}
+// stream samples a symbol hands to the next one's FIR (the LDS keeps room for one without a channel)
+constexpr int tx_tails(int L) { return L > 1 ? L - 1 : 1; }
+// The dynamic LDS of k_tx at BLK threads for the plan's LUT length, staged bit words per symbol,
+// FIR tail (tx_tails) and row slot: the kernel's layout and the launcher's byte count
+template <typename R>
+struct TxLds {
+    cpx<R> *tw, *lut, *h, *hsw, *tails, *tt;
+    AxisInfo* axis;
+    unsigned char* rowmem;
+    uint32_t *words, *sce;
+    double* red;
+};
+template <typename R, int LOGN, int FB, int LT, int BLK, typename CV>
+__host__ __device__ __forceinline__ constexpr TxLds<R> tx_carve(CV& cv, int lut_len, int words_per_sym, int tls,
+                                                                int slot) {
+    using G = Geo<LOGN, BLK>;
+    using C = cpx<R>;
+    // complex128 flat and window-FIR TX: a row of reals (fft_reg_split)
+    // (the window FIR passes its stream through the row of reals twice: real, then imaginary parts)
+    constexpr bool ROW_REAL = split_rows<R, FB>() && LT >= 0;
+    constexpr bool TT = uses_tt<R, LOGN, FB>();
+    TxLds<R> m{};
+    m.tw = cv.template take<C>(TT ? 0 : 128);  // two-level twiddles (generic kernel, complex128 N > 1024)
+    if constexpr (FB == 0) m.lut = cv.template take<C>(lut_len);  // (throughput kernels: static LDS)
+    m.h = cv.template take<C>(32);
+    m.hsw = cv.template take<C>(FB > 0 && LT > 0 ? 32 : 0);  // window FIR: the taps swizzled, (-im, re)
+    m.axis = cv.template take<AxisInfo>(kMaxLuts);
+    m.rowmem = cv.template take<unsigned char>((size_t)G::SPB * slot * (ROW_REAL ? sizeof(R) : sizeof(C)));
+    m.tails = cv.template take<C>((size_t)G::SPB * tls);
+    m.words = cv.template take<uint32_t>(FB ? 0 : (size_t)G::SPB * words_per_sym);  // reference bits
+    m.red = cv.template take<double>(BLK / 64);
+    m.tt = cv.template take<C>(TT ? tt_size(LOGN) : 0);  // throughput kernel: inverse per-pass twiddles
+    // adaptive throughput kernel: per subcarrier (LUT offset << 8 | tx bit mask); unused
+    // subcarriers point at a zero entry appended to the LUT pool
+    m.sce = cv.template take<uint32_t>(FB == 1 ? G::N : 0);
+    return m;
+}
+// LT (throughput TX): 0 flat channel; 4 / 8 multipath with <= LT taps through the register
+// window FIR (N >= 256, cp <= TPS); -1 any multipath (run-time loop over taps).  ZPW: the complex128
+// window FIR with the zero-padding guard (and its run-time flat path for a one-tap channel) compiled
+// in; without it (cyclic prefix, L > 1: the bench configs) the kernel needs ~139 VGPRs instead of
+// 205-227 (3 waves per SIMD would fit with nothing spilled; measured no faster, DESIGN.md section 4)
+template <typename R, int FB, int LOGN, int LT, bool ZPW = false>
+constexpr int tx_block() {
+    if constexpr (sizeof(R) == 8 && FB > 0 && LT != 0) {
+        // OFDM_F64_FIR_BLOCK threads if their LDS, static and dynamic, fits on the nominal channel
+        // of these shapes (cp = 32, 8 taps)
+        constexpr int BLK = OFDM_F64_FIR_BLOCK;
+        CarveSize lds;
+        tx_carve<R, LOGN, FB, LT, BLK>(lds, 0, 0, tx_tails(8), tx_row_slot<R, LOGN, FB, LT>(tx_slot(LOGN, 32, 8), 32));
+        return lds.bytes + tx_static_lds<R, FB, LT>() <= kLdsPerCu ? BLK : 256;
+    }
+    if (sizeof(R) == 8 && FB > 0) return OFDM_F64_TX_BLOCK;
+    return FB > 0 && LOGN <= 10 ? (LT != 0 ? OFDM_TX_MP_BLOCK : OFDM_TX_FAST_BLOCK) : kBlock;
+}
+constexpr int block_waves(int blk, int dflt) { return blk >= 512 ? 4 : dflt; }
+template <typename R, int FB, int LOGN, int LT, bool ZPW = false>
+constexpr int tx_waves() {
+    if (sizeof(R) == 8 && FB > 0) {
+        if (LT == 0) return OFDM_F64_TX_WAVES;
+        return LOGN >= 12 ? OFDM_F64_FIR_WAVES_4K : OFDM_F64_FIR_WAVES;
+    }
+    if (FB > 0 && LT > 0 && LOGN > 10) return OFDM_TX_BIG_WFIR_WAVES;
+    return block_waves(tx_block<R, FB, LOGN, LT>(), FB > 0 && LT > 0 ? OFDM_TX_WFIR_WAVES : OFDM_TX_WAVES);
+}
+
 // Each symbol group walks `chunk` consecutive OFDM symbols so the FIR tail (last L-1
 // stream samples of the previous symbol) is carried in LDS; the first symbol of a chunk
 // regenerates its predecessor's tail (one extra IFFT per chunk, L > 1 only).
@@ -588,35 +635,25 @@ __global__ __launch_bounds__((tx_block<R, FB, LOGN, LT, ZPW>()), (tx_waves<R, FB
     const int ystride = ZP_OK ? cm.ystride : N;  // stored samples per OFDM symbol: N, or N + cp (ZP)
     const int cp = cm.cp, L = LT != 0 ? a.L : 1;
     const int slot = a.slot;  // complex elements per symbol row (>= PADN and >= L-1+cp+N)
-    const int tls = L > 1 ? L - 1 : 1;
+    const int tls = L > 1 ? L - 1 : 1;  // tx_tails(L) spelled out (through the call the LT = -1 kernels compile differently)
     constexpr bool TT = uses_tt<R, LOGN, FB>();
-    // complex128 flat and window-FIR TX: a row of reals (fft_reg_split)
-    // (the window FIR passes its stream through the row of reals twice: real, then imaginary parts)
-    constexpr bool ROW_REAL = split_rows<R, FB>() && LT >= 0;
-    Carve cv(ofdm_smem);
-    C* tw = cv.take<C>(TT ? 0 : 128);  // two-level twiddles (generic kernel, complex128 N > 1024)
+    constexpr bool ROW_REAL = split_rows<R, FB>() && LT >= 0;  // (as tx_carve)
     // throughput kernels: the LUT in static LDS at a link-time address, so an element's LUT read
-    // is addressed by its index bits alone (2^FB entries; adaptive: the pool + a zero entry);
-    // generic kernel: dynamic
-    constexpr int LUT_STATIC = FB == 1 ? kMaxLut + 1 : (FB > 1 ? (1 << FB) : 1);
+    // is addressed by its index bits alone; generic kernel: dynamic
+    constexpr int LUT_STATIC = tx_lut_static<FB>();
     __shared__ C lut_s[LUT_STATIC];
     // complex128 multipath TX of square QAM: the LUT as its two axis tables (tx_sep_lut)
     constexpr bool SEP = tx_sep_lut<R, FB, LT>();
     constexpr int HB = FB / 2, SIDE = 1 << HB;
-    __shared__ R sep_s[SEP ? 2 * SIDE : 1];
-    C* lut = FB > 0 ? lut_s : cv.take<C>(cm.lut_len);
-    C* h = cv.take<C>(32);
-    C* hsw = cv.take<C>(WFIR ? 32 : 0);  // window FIR: the taps swizzled, (-im, re)
-    AxisInfo* axis = cv.take<AxisInfo>(kMaxLuts);
-    unsigned char* rowmem = cv.take<unsigned char>((size_t)G::SPB * slot * (ROW_REAL ? sizeof(R) : sizeof(C)));
-    C* tails = cv.take<C>((size_t)G::SPB * tls);
-    uint32_t* words = cv.take<uint32_t>(FB ? 0 : (size_t)G::SPB * cm.words_per_sym);  // reference bits
-    double* red = cv.take<double>(BLK / 64);
+    __shared__ R sep_s[tx_sep_static<R, FB, LT>()];
+    Carve cv(ofdm_smem);
+    const TxLds<R> lds = tx_carve<R, LOGN, FB, LT, BLK>(cv, cm.lut_len, cm.words_per_sym, tls, slot);
+    C *tw = lds.tw, *lut = FB > 0 ? lut_s : lds.lut, *h = lds.h, *hsw = lds.hsw, *tails = lds.tails, *tt = lds.tt;
+    AxisInfo* axis = lds.axis;
+    unsigned char* rowmem = lds.rowmem;
+    uint32_t *words = lds.words, *sce = lds.sce;
+    double* red = lds.red;
     constexpr int TTS = TT ? tt_size(LOGN) : 0;
-    C* tt = cv.take<C>(TTS);  // throughput kernel: inverse per-pass twiddles
-    // adaptive throughput kernel: per subcarrier (LUT offset << 8 | tx bit mask); unused
-    // subcarriers point at a zero entry appended to the LUT pool
-    uint32_t* sce = cv.take<uint32_t>(FB == 1 ? N : 0);
 
     // the tables' global reads issued first (Staged), then the LDS writes
     constexpr bool FOLD_H0 = FB > 0 && LT == 0;
@@ -1173,6 +1210,55 @@ __global__ __launch_bounds__((tx_block<R, FB, LOGN, LT, ZPW>()), (tx_waves<R, FB
 }
 
 // ============================================================ fused RX
+// static (__shared__) LDS of k_rx beside its dynamic rows: the noise phase table, and for the
+// complex128 throughput kernels the table widened to double (Mwc64x::add_noise64)
+template <typename R, int FB>
+constexpr int rx_ntab64_static() { return sizeof(R) == 8 && FB > 0 ? kNoisePhases : 1; }
+template <typename R, int FB>
+constexpr size_t rx_static_lds() { return kNoisePhases * sizeof(f32x2) + rx_ntab64_static<R, FB>() * sizeof(f64x2); }
+// per-pass twiddles of a throughput receiver: the forward ones, plus the inverse ones for SC-OFDM's IFFT
+template <typename R, int LOGN, int FB>
+constexpr int rx_tts(bool scm) {
+    constexpr int TTS = uses_tt<R, LOGN, FB>() ? tt_size(LOGN) : 0;
+    return FB > 1 && scm ? 2 * TTS : TTS;
+}
+// The dynamic LDS of k_rx for the plan's staged bit words per symbol and the twiddles the kernel
+// stages (rx_tts): the kernel's layout and the launcher's byte count
+template <typename R>
+struct RxLds {
+    // adaptive: per-order slicer constants (complex128: double entries)
+    using OP = std::conditional_t<sizeof(R) == 8, OrderParams64, OrderParams>;
+    cpx<R> *tw, *tt, *eqt;
+    AxisInfo* axis;
+    unsigned char* rowmem;
+    uint32_t* words;
+    R* red;
+    unsigned long long* redc;
+    OP* ordt;
+};
+template <typename R, int LOGN, int EQ, int FB, bool MV, typename CV>
+__host__ __device__ __forceinline__ constexpr RxLds<R> rx_carve(CV& cv, int words_per_sym, int tts_all) {
+    constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV>();
+    using G = Geo<LOGN, BLK>;
+    using C = cpx<R>;
+    constexpr bool SPLIT = split_rows<R, FB>();  // complex128 throughput: rows of reals
+    RxLds<R> m{};
+    // two-level twiddles (generic kernel, complex128 N > 1024)
+    m.tw = cv.template take<C>(uses_tt<R, LOGN, FB>() ? 0 : 128);
+    m.axis = cv.template take<AxisInfo>(kMaxLuts);
+    m.rowmem = cv.template take<unsigned char>((size_t)G::SPB * G::PADN * (SPLIT ? sizeof(R) : sizeof(C)));
+    m.words = cv.template take<uint32_t>(FB ? 0 : (size_t)G::SPB * words_per_sym);  // reference bits
+    m.red = cv.template take<R>(BLK / 64);
+    m.redc = cv.template take<unsigned long long>(BLK / 64);
+    m.tt = cv.template take<C>(tts_all);
+    m.ordt = cv.template take<typename RxLds<R>::OP>(FB == 1 ? 8 : 0);
+    // throughput kernels with an equaliser: the per-subcarrier coefficient staged in LDS once
+    // per workgroup (ZF: 1/H; MMSE: conj(H), |H|^2 recomputed from it) -- read from the plan's
+    // global table, every element paid an L2 round trip with a vmcnt(0) per symbol
+    m.eqt = cv.template take<C>(eq_in_lds<R, FB, LOGN, EQ>() ? G::N : 0);
+    return m;
+}
+
 // EQ: OFDM_EQ_* fixed at compile time (throughput kernel) or -1 = from the plan.
 // MV: SC-OFDM and zero padding compiled in (run-time flags); complex128 compiles them out of the
 // cyclic-prefix OFDM kernels (rx_eq)
@@ -1202,29 +1288,23 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB,
     // (from its phase word) addresses it with no add
     __shared__ f32x2 ntab[kNoisePhases];
     // complex128 throughput kernels: the table widened to double (Mwc64x::add_noise64)
-    __shared__ f64x2 ntab64_s[F64_FAST ? kNoisePhases : 1];
+    __shared__ f64x2 ntab64_s[rx_ntab64_static<R, FB>()];
     f64x2* ntab64 = F64_FAST ? ntab64_s : nullptr;
     Carve cv(ofdm_smem);
     constexpr bool TT = uses_tt<R, LOGN, FB>();
     constexpr bool SPLIT = split_rows<R, FB>();  // complex128 throughput: rows of reals
-    C* tw = cv.take<C>(TT ? 0 : 128);  // two-level twiddles (generic kernel, complex128 N > 1024)
-    AxisInfo* axis = cv.take<AxisInfo>(kMaxLuts);
-    unsigned char* rowmem = cv.take<unsigned char>((size_t)G::SPB * G::PADN * (SPLIT ? sizeof(R) : sizeof(C)));
-    uint32_t* words = cv.take<uint32_t>(FB ? 0 : (size_t)G::SPB * cm.words_per_sym);  // reference bits
-    R* red = cv.take<R>(BLK / 64);
-    unsigned long long* redc = cv.take<unsigned long long>(BLK / 64);
     constexpr int TTS = TT ? tt_size(LOGN) : 0;
-    // throughput kernel: forward per-pass twiddles, plus the inverse ones for SC-OFDM's IFFT
-    const int tts_all = FB > 1 && scm ? 2 * TTS : TTS;
-    C* tt = cv.take<C>(tts_all);
-    // adaptive: per-order slicer constants (complex128: double entries)
-    using OP = std::conditional_t<sizeof(R) == 8, OrderParams64, OrderParams>;
-    OP* ordt = cv.take<OP>(FB == 1 ? 8 : 0);
-    // throughput kernels with an equaliser: the per-subcarrier coefficient staged in LDS once
-    // per workgroup (ZF: 1/H; MMSE: conj(H), |H|^2 recomputed from it) -- read from the plan's
-    // global table, every element paid an L2 round trip with a vmcnt(0) per symbol
-    constexpr bool EQ_LDS = eq_in_lds<R, FB, LOGN, EQ>();
-    C* eqt = cv.take<C>(EQ_LDS ? N : 0);
+    const int tts_all = rx_tts<R, LOGN, FB>(scm);
+    const RxLds<R> lds = rx_carve<R, LOGN, EQ, FB, MV>(cv, cm.words_per_sym, tts_all);
+    C *tw = lds.tw, *tt = lds.tt, *eqt = lds.eqt;
+    AxisInfo* axis = lds.axis;
+    unsigned char* rowmem = lds.rowmem;
+    uint32_t* words = lds.words;
+    R* red = lds.red;
+    unsigned long long* redc = lds.redc;
+    using OP = typename RxLds<R>::OP;
+    OP* ordt = lds.ordt;
+    constexpr bool EQ_LDS = eq_in_lds<R, FB, LOGN, EQ>();  // (rx_carve)
     // otherwise (throughput kernels at N = 4096, and the complex64 generic kernel) the lane's
     // coefficients are loaded before the FFT each symbol (L2-resident), so their latency hides
     // behind it instead of stalling each element of the equaliser

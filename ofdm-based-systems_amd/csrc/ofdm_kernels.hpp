@@ -15,7 +15,9 @@
 
 namespace ofdm {
 
-// LDS carve helper: 16-byte aligned bump allocator over the dynamic LDS region.
+// LDS carve helpers: 16-byte aligned bump allocation.  The dynamic LDS layout of k_rows, k_tx and
+// k_rx is one take<> sequence each (rows_carve, tx_carve, rx_carve): the kernel runs it with Carve
+// over its LDS region, the launcher with CarveSize, which only adds up the bytes to ask for.
 struct Carve {
     unsigned char* p;
     __device__ explicit Carve(unsigned char* base) : p(base) {}
@@ -26,10 +28,34 @@ struct Carve {
         return r;
     }
 };
+struct CarveSize {
+    size_t bytes = 0;
+    template <typename T>
+    constexpr T* take(size_t n) {
+        bytes += (n * sizeof(T) + 15) & ~size_t(15);
+        return nullptr;
+    }
+};
 
 extern __shared__ __attribute__((aligned(16))) unsigned char ofdm_smem[];
 
 // ============================================================ operator rows kernel
+template <typename R>
+struct RowsLds {
+    cpx<R> *tw, *data;
+    R *rowscale, *red;
+};
+template <typename R, int LOGN, typename CV>
+__host__ __device__ __forceinline__ constexpr RowsLds<R> rows_carve(CV& cv) {
+    using G = Geo<LOGN>;
+    RowsLds<R> m{};
+    m.tw = cv.template take<cpx<R>>(128);
+    m.data = cv.template take<cpx<R>>((size_t)G::SPB * G::PADN);
+    m.rowscale = cv.template take<R>(G::SPB);
+    m.red = cv.template take<R>(kBlock);
+    return m;
+}
+
 // One workgroup iteration = SPB rows of N.  MODE: 0 = FFT (in place), 1 = modulate
 // (inverse FFT + cyclic prefix), 2 = demodulate (strip prefix, forward FFT, equalise).
 template <typename R, int LOGN, int MODE>
@@ -37,10 +63,7 @@ __global__ __launch_bounds__(kBlock) void k_rows(RowsArgs a) {
     using G = Geo<LOGN>;
     using C = cpx<R>;
     Carve cv(ofdm_smem);
-    C* tw = cv.take<C>(128);
-    C* data = cv.take<C>((size_t)G::SPB * G::PADN);
-    R* rowscale = cv.take<R>(G::SPB);
-    R* red = cv.take<R>(kBlock);
+    const auto [tw, data, rowscale, red] = rows_carve<R, LOGN>(cv);
     load_twiddles<R>(tw, (const C*)a.tw);
     __syncthreads();
 

@@ -18,13 +18,11 @@ namespace ofdm {
 #ifdef OFDM_AB_ONLY
 #define OFDM_LOGN_CASES(X) X(10) X(11) X(12)
 #define OFDM_FB_CASES(X) X(6) X(8)
-#define OFDM_FB64_CASES(X) X(6) X(8)
 #else
 #define OFDM_LOGN_CASES(X) \
     X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12)
+// throughput kernels, both precisions: square QAM (4..256) and the reference's 4..32-PSK
 #define OFDM_FB_CASES(X) X(2) X(3) X(4) X(5) X(6) X(8)
-// complex128 throughput kernels: square QAM (4..256) and the reference's 4..32-PSK
-#define OFDM_FB64_CASES(X) X(2) X(3) X(4) X(5) X(6) X(8)
 #endif
 
 template <typename F>
@@ -46,10 +44,6 @@ constexpr hipError_t kOutOfRange = hipErrorInvalidValue;
 #endif
 
 constexpr int kFastMinLogN = 6;  // throughput specialisations for N >= 64
-// LDS per CU on gfx950: a throughput-kernel instantiation whose LDS would exceed it (a shape the plan
-// allows but the specialised layout cannot hold) runs the generic kernel instead of failing at
-// launch (tests/test_gpu_edges.py::test_lds_limit_shapes_run)
-constexpr size_t kLdsPerCu = 160 * 1024;
 
 static inline int clamp_grid(int64_t want) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(want, kMaxGrid));
@@ -57,7 +51,9 @@ static inline int clamp_grid(int64_t want) {
 
 template <typename R, int LOGN, int MODE>
 static hipError_t rows_one(const RowsArgs& a, hipStream_t s) {
-    const size_t sm = smem_rows<R>(LOGN);
+    CarveSize lds;
+    rows_carve<R, LOGN>(lds);
+    const size_t sm = lds.bytes;
     auto fn = k_rows<R, LOGN, MODE>;
     static const hipError_t attr = set_smem(fn, sm);
     if (attr != hipSuccess) return attr;
@@ -82,59 +78,47 @@ hipError_t launch_rows(int logn, int mode, const RowsArgs& a, hipStream_t s) {
 #undef OFDM_ROWS_CASE
 }
 
+// The elementwise kernels: `grid` workgroups of kBlock threads, no dynamic LDS (per_block: one
+// workgroup per kBlock items of n); nothing to do for n <= 0
+template <typename K, typename A>
+static hipError_t launch_flat(K fn, int grid, const A& a, hipStream_t s) {
+    (void)hipGetLastError();  // stale errors were reported by their own calls
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+}
+template <typename K, typename A>
+static hipError_t launch_flat_n(K fn, int64_t n, bool per_block, const A& a, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    return launch_flat(fn, clamp_grid(per_block ? (n + kBlock - 1) / kBlock : n), a, s);
+}
+
 template <typename R>
 hipError_t launch_equalize(const EqArgs& a, hipStream_t s) {
-    if (a.n_rows <= 0) return hipSuccess;
-    (void)hipGetLastError();  // stale errors were reported by their own calls
-    hipLaunchKernelGGL(k_equalize<R>, dim3(clamp_grid(a.n_rows)), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+    return launch_flat_n(k_equalize<R>, a.n_rows, false, a, s);  // a workgroup per row
 }
-
 template <typename R>
 hipError_t launch_map(const MapArgs& a, hipStream_t s) {
-    if (a.n_out <= 0) return hipSuccess;
-    (void)hipGetLastError();  // stale errors were reported by their own calls
-    hipLaunchKernelGGL(k_map<R>, dim3(clamp_grid((a.n_out + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+    return launch_flat_n(k_map<R>, a.n_out, true, a, s);
 }
-
 template <typename R>
 hipError_t launch_demap(const DemapArgs& a, hipStream_t s) {
-    if (a.n_bytes <= 0) return hipSuccess;
-    (void)hipGetLastError();  // stale errors were reported by their own calls
-    hipLaunchKernelGGL(k_demap<R>, dim3(clamp_grid((a.n_bytes + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+    return launch_flat_n(k_demap<R>, a.n_bytes, true, a, s);
 }
-
 template <typename R>
 hipError_t launch_demap_count(const DemapCountArgs& a, hipStream_t s) {
-    const int64_t n = a.n_sym * a.n_fft;
-    if (n <= 0) return hipSuccess;
-    (void)hipGetLastError();  // stale errors were reported by their own calls
-    hipLaunchKernelGGL(k_demap_count<R>, dim3(clamp_grid((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+    return launch_flat_n(k_demap_count<R>, a.n_sym * a.n_fft, true, a, s);
 }
-
 template <typename R>
 hipError_t launch_conv(const ConvArgs& a, int grid, hipStream_t s) {
-    (void)hipGetLastError();  // stale errors were reported by their own calls
-    hipLaunchKernelGGL(k_conv<R>, dim3(grid), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+    return launch_flat(k_conv<R>, grid, a, s);
 }
-
 template <typename R>
 hipError_t launch_power(const PowerArgs& a, int grid, hipStream_t s) {
-    (void)hipGetLastError();  // stale errors were reported by their own calls
-    hipLaunchKernelGGL(k_power<R>, dim3(grid), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+    return launch_flat(k_power<R>, grid, a, s);
 }
-
 template <typename R>
 hipError_t launch_awgn(const AwgnArgs& a, hipStream_t s) {
-    if (a.len <= 0) return hipSuccess;
-    (void)hipGetLastError();  // stale errors were reported by their own calls
-    hipLaunchKernelGGL(k_awgn<R>, dim3(clamp_grid((a.len + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+    return launch_flat_n(k_awgn<R>, a.len, true, a, s);
 }
 
 // Workgroups of a kernel resident on the device at once (occupancy x CUs), cached per kernel,
@@ -191,22 +175,10 @@ template <typename R, int LOGN, int FB, int LT, bool ZPW = false, bool REF = fal
 static hipError_t tx_launch(const TxArgs& a0, int* grid, hipStream_t s) {
     constexpr int BLK = tx_block<R, FB, LOGN, LT, ZPW>();
     TxArgs a = a0;
-    if (FB > 0 && LT > 0) {
-        if constexpr (sizeof(R) == 8) {
-            // complex128: the row of reals carries half a symbol's stream as complex samples, half 0's
-            // m in [-(LT-1), cp + N/2) at wfir_in(A8 - cp + LT - 1 + m), and N / 2 transposed outputs
-            const int A8 = (a.c.cp + 7) & ~7;
-            a.slot = std::max(a.slot, 2 * (wfir_in(A8 + (1 << LOGN) / 2 + LT - 2, LT) + 1));
-            a.slot = std::max(a.slot, 2 * (wfir_out((1 << LOGN) / 2 - 1) + 1));
-        } else {
-            // window FIR row: stream samples [-(LT-1), N+cp) at fir_pad(R0 + m)
-            const int A = (a.c.cp + 15) & ~15, R0 = A - a.c.cp + LT - 1;
-            a.slot = std::max(a.slot, fir_pad(R0 + (1 << LOGN) + a.c.cp) + 1);
-        }
-    }
-    const size_t sm = smem_tx<R>(LOGN, BLK, FB > 0 ? 0 : a.c.lut_len, a.c.words_per_sym, a.L, a.slot,
-                                 uses_tt<R, LOGN, FB>() ? tt_size(LOGN) : 0, FB > 0 && LT > 0,
-                                 FB == 1 ? (size_t)4 << LOGN : 0, FB > 0, split_rows<R, FB>() && LT >= 0);
+    a.slot = tx_row_slot<R, LOGN, FB, LT>(a.slot, a.c.cp);
+    CarveSize lds;
+    tx_carve<R, LOGN, FB, LT, BLK>(lds, a.c.lut_len, a.c.words_per_sym, tx_tails(a.L), a.slot);
+    const size_t sm = lds.bytes;
     if constexpr (FB > 0) {
         if (sm + tx_static_lds<R, FB, LT>() > kLdsPerCu) return tx_launch<R, LOGN, 0, -1>(a0, grid, s);
     }
@@ -221,11 +193,12 @@ static hipError_t tx_launch(const TxArgs& a0, int* grid, hipStream_t s) {
     return hipGetLastError();
 }
 
-// throughput TX by channel length: flat / window FIR (<= 4 or <= 8 taps) / run-time taps
-template <typename R, int LOGN, int FB>
+// throughput TX by channel length: flat / window FIR (<= 4 or <= 8 taps) / run-time taps (REF, see
+// ref_shape: the generic kernel)
+template <typename R, int LOGN, int FB, bool REF = false>
 static hipError_t tx_fast(const TxArgs& a, int* grid, hipStream_t s) {
     constexpr int TPS = Geo<LOGN>::TPS;
-    if (a.L == 1 && !a.c.zpad) return tx_launch<R, LOGN, FB, 0>(a, grid, s);
+    if (a.L == 1 && !a.c.zpad) return tx_launch<R, LOGN, FB, 0, false, REF>(a, grid, s);
     if constexpr (LOGN >= 8) {
         // the complex64 register window assumes a cyclic prefix; the complex128 one takes zero padding
         if (a.c.cp <= TPS && (!a.c.zpad || sizeof(R) == 8)) {
@@ -236,11 +209,11 @@ static hipError_t tx_fast(const TxArgs& a, int* grid, hipStream_t s) {
                     if (a.L <= 8) return tx_launch<R, LOGN, FB, 8, true>(a, grid, s);
                 }
             }
-            if (a.L <= 4) return tx_launch<R, LOGN, FB, 4>(a, grid, s);
-            if (a.L <= 8) return tx_launch<R, LOGN, FB, 8>(a, grid, s);
+            if (a.L <= 4) return tx_launch<R, LOGN, FB, 4, false, REF>(a, grid, s);
+            if (a.L <= 8) return tx_launch<R, LOGN, FB, 8, false, REF>(a, grid, s);
         }
     }
-    return tx_launch<R, LOGN, FB, -1>(a, grid, s);
+    return tx_launch<R, LOGN, REF ? 0 : FB, -1>(a, grid, s);
 }
 
 // Reference streams (the caller's bits; RX: and normals) on the bench configs' shapes go through the
@@ -253,59 +226,36 @@ static hipError_t tx_fast(const TxArgs& a, int* grid, hipStream_t s) {
 template <typename R, int LOGN>
 constexpr int ref_fb() { return sizeof(R) == 8 ? (LOGN == 10 ? 6 : LOGN == 11 ? 1 : LOGN == 12 ? 8 : 0) : 0; }
 
+// What the adaptive throughput kernels (FB = 1) take: adaptive bit loading over the reference's
+// square-QAM LUTs (upat: orders <= 256), OFDM with a cyclic prefix
+static inline bool adaptive_fast(const TxRxCommon& c) { return c.adaptive && c.upat && !c.scm && !c.zpad && !c.nn; }
+// What the fixed-order throughput kernels (FB = b) take: fixed square QAM or the reference's
+// 4/8/16/32-PSK (psk_m > 0; odd bits: its 8/32-PSK only), OFDM or SC-OFDM, cyclic prefix or zero padding
+static inline bool fixed_fast(const TxRxCommon& c) {
+    return !c.adaptive && (!c.nn || c.psk_m > 0) && (c.b % 2 == 0 || c.psk_m > 0);
+}
+
 template <typename R, int LOGN>
 static bool ref_shape(const TxRxCommon& c) {
     constexpr int FB = ref_fb<R, LOGN>();
     if (FB == 0 || c.bits == nullptr || c.nn || c.scm || c.zpad) return false;
-    if (FB == 1) return c.adaptive && c.upat;  // (upat: square QAM of orders <= 256, the adaptive kernels')
+    if (FB == 1) return adaptive_fast(c);
     return !c.adaptive && c.psk_m == 0 && c.b == FB;
 }
 
-template <typename R, int LOGN>
-static hipError_t tx_ref(const TxArgs& a, int* grid, hipStream_t s) {
-    constexpr int FB = ref_fb<R, LOGN>();
-    if constexpr (FB > 0) {
-        constexpr int TPS = Geo<LOGN>::TPS;
-        if (a.L == 1) return tx_launch<R, LOGN, FB, 0, false, true>(a, grid, s);
-        if (a.c.cp <= TPS) {
-            if (a.L <= 4) return tx_launch<R, LOGN, FB, 4, false, true>(a, grid, s);
-            if (a.L <= 8) return tx_launch<R, LOGN, FB, 8, false, true>(a, grid, s);
-        }
-    }
-    return tx_launch<R, LOGN, 0, -1>(a, grid, s);
-}
-
-// Throughput configuration (complex64, fixed square QAM or the reference's 4/8/16/32-PSK (psk_m > 0),
-// Philox bits; N >= 64; OFDM or SC-OFDM, cyclic prefix or zero padding) -> the kernel specialised on the bits per
-// subcarrier; adaptive bit loading over the reference's square-QAM LUTs (OFDM, cyclic
-// prefix) -> the adaptive throughput kernel (FB = 1); anything else -> the generic kernel.
+// Throughput configuration (Philox bits, N >= 64): fixed_fast -> the kernel specialised on the bits
+// per subcarrier; adaptive_fast -> the adaptive throughput kernel (FB = 1); anything else -> the
+// generic kernel.
 template <typename R, int LOGN>
 static hipError_t tx_one(const TxArgs& a, int* grid, hipStream_t s) {
-    if (ref_shape<R, LOGN>(a.c)) return tx_ref<R, LOGN>(a, grid, s);
-    if constexpr (sizeof(R) == 8 && LOGN >= kFastMinLogN) {
-        // complex128 throughput kernels: device bits; square QAM with adaptive loading (OFDM, cyclic
-        // prefix); fixed square QAM or the reference's 4..32-PSK, OFDM or SC-OFDM, cyclic prefix or
-        // zero padding
-        if (a.c.adaptive && a.c.upat && a.c.bits == nullptr && !a.c.scm && !a.c.zpad && !a.c.nn)
-            return tx_fast<R, LOGN, 1>(a, grid, s);
-        if (!a.c.adaptive && a.c.bits == nullptr && (!a.c.nn || a.c.psk_m > 0) && (a.c.b % 2 == 0 || a.c.psk_m > 0)) {
-#define OFDM_TX_FB64(F) \
-    case F:                \
-        return tx_fast<R, LOGN, F>(a, grid, s);
-            switch (a.c.b) {
-                OFDM_FB64_CASES(OFDM_TX_FB64)
-                default: break;
-            }
-#undef OFDM_TX_FB64
-        }
+    if constexpr (ref_fb<R, LOGN>() > 0) {
+        if (ref_shape<R, LOGN>(a.c)) return tx_fast<R, LOGN, ref_fb<R, LOGN>(), true>(a, grid, s);
     }
-    if constexpr (sizeof(R) == 4 && LOGN >= kFastMinLogN) {
-        if (a.c.adaptive && a.c.upat && a.c.bits == nullptr && !a.c.scm && !a.c.zpad && !a.c.nn)
-            return tx_fast<R, LOGN, 1>(a, grid, s);
-        // OFDM / SC, CP / ZP, QAM / PSK (odd bits: the reference's 8/32-PSK only)
-        if (!a.c.adaptive && a.c.bits == nullptr && (!a.c.nn || a.c.psk_m > 0) && (a.c.b % 2 == 0 || a.c.psk_m > 0)) {
+    if constexpr (LOGN >= kFastMinLogN) {
+        if (a.c.bits == nullptr && adaptive_fast(a.c)) return tx_fast<R, LOGN, 1>(a, grid, s);
+        if (a.c.bits == nullptr && fixed_fast(a.c)) {
 #define OFDM_TX_FB(F) \
-    case F:              \
+    case F:           \
         return tx_fast<R, LOGN, F>(a, grid, s);
             switch (a.c.b) {
                 OFDM_FB_CASES(OFDM_TX_FB)
@@ -333,11 +283,9 @@ hipError_t launch_tx(int logn, const TxArgs& a, int* grid, hipStream_t s) {
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false>
 static hipError_t rx_launch(const RxArgs& a, int* grid, hipStream_t s) {
     constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV>();
-    const size_t sm = smem_rx<R>(LOGN, BLK, a.c.words_per_sym,
-                                 uses_tt<R, LOGN, FB>() ? tt_size(LOGN) * (FB > 1 && a.c.scm ? 2 : 1) : 0,
-                                 (FB == 1 ? 8 * (sizeof(R) == 8 ? sizeof(OrderParams64) : sizeof(OrderParams)) : 0) +
-                                     (eq_in_lds<R, FB, LOGN, EQ>() ? ((size_t)2 * sizeof(R)) << LOGN : 0),
-                                 FB > 0, split_rows<R, FB>());
+    CarveSize lds;
+    rx_carve<R, LOGN, EQ, FB, MV>(lds, a.c.words_per_sym, rx_tts<R, LOGN, FB>(a.c.scm));
+    const size_t sm = lds.bytes;
     if constexpr (FB > 0) {
         if (sm + rx_static_lds<R, FB>() > kLdsPerCu) return rx_launch<R, LOGN, -1, 0, true>(a, grid, s);
     }
@@ -363,9 +311,9 @@ static hipError_t rx_eq(const RxArgs& a, int* grid, hipStream_t s) {
     return rx_launch<R, LOGN, OFDM_EQ_MMSE, FB, MV, REF>(a, grid, s);
 }
 
-// Throughput configuration (complex64, fixed square QAM or the reference's 4/8/16/32-PSK (psk_m > 0),
-// Philox bits and noise, no received-symbol tap; N >= 64) -> kernel specialised on bits and
-// equaliser; anything else -> the generic kernel.
+// Throughput configuration (Philox bits and noise, no received-symbol tap; N >= 64): fixed_fast ->
+// the kernel specialised on bits and equaliser; adaptive_fast -> the adaptive one; anything else ->
+// the generic kernel.
 template <typename R, int LOGN>
 static hipError_t rx_one(const RxArgs& a, int* grid, hipStream_t s) {
     if constexpr (ref_fb<R, LOGN>() > 0) {
@@ -376,32 +324,16 @@ static hipError_t rx_one(const RxArgs& a, int* grid, hipStream_t s) {
         if (ref_shape<R, LOGN>(a.c) && a.nr != nullptr && a.z_out == nullptr)
             return rx_eq<R, LOGN, ref_fb<R, LOGN>(), ref_fb<R, LOGN>() == 1, true>(a, grid, s);
     }
-    if constexpr (sizeof(R) == 8 && LOGN >= kFastMinLogN) {
-        if (a.c.adaptive && a.c.upat && a.c.bits == nullptr && a.nr == nullptr && a.z_out == nullptr &&
-            !a.c.scm && !a.c.zpad && !a.c.nn)
-            return rx_eq<R, LOGN, 1>(a, grid, s);
-        if (!a.c.adaptive && a.c.bits == nullptr && a.nr == nullptr && a.z_out == nullptr &&
-            (!a.c.nn || a.c.psk_m > 0) && (a.c.b % 2 == 0 || a.c.psk_m > 0)) {
-#define OFDM_RX_FB64(F)                                                              \
-    case F:                                                                              \
-        return (a.c.scm || a.c.zpad) ? rx_eq<R, LOGN, F, true>(a, grid, s)               \
-                                     : rx_eq<R, LOGN, F, false>(a, grid, s);
-            switch (a.c.b) {
-                OFDM_FB64_CASES(OFDM_RX_FB64)
-                default: break;
-            }
-#undef OFDM_RX_FB64
-        }
-    }
-    if constexpr (sizeof(R) == 4 && LOGN >= kFastMinLogN) {
-        if (a.c.adaptive && a.c.upat && a.c.bits == nullptr && a.nr == nullptr && a.z_out == nullptr &&
-            !a.c.scm && !a.c.zpad && !a.c.nn)
-            return rx_eq<R, LOGN, 1>(a, grid, s);
-        if (!a.c.adaptive && a.c.bits == nullptr && a.nr == nullptr && a.z_out == nullptr &&
-            (!a.c.nn || a.c.psk_m > 0) && (a.c.b % 2 == 0 || a.c.psk_m > 0)) {  // OFDM / SC, CP / ZP, QAM / PSK
-#define OFDM_RX_FB(F) \
-    case F:              \
-        return rx_eq<R, LOGN, F>(a, grid, s);
+    if constexpr (LOGN >= kFastMinLogN) {
+        const bool streams = a.c.bits == nullptr && a.nr == nullptr && a.z_out == nullptr;
+        if (streams && adaptive_fast(a.c)) return rx_eq<R, LOGN, 1>(a, grid, s);
+        if (streams && fixed_fast(a.c)) {
+#define OFDM_RX_FB(F)                                                                      \
+    case F:                                                                                \
+        if constexpr (sizeof(R) == 8) { /* the modem variants in kernels of their own: rx_eq */ \
+            if (!a.c.scm && !a.c.zpad) return rx_eq<R, LOGN, F, false>(a, grid, s);        \
+        }                                                                                  \
+        return rx_eq<R, LOGN, F, true>(a, grid, s);
             switch (a.c.b) {
                 OFDM_FB_CASES(OFDM_RX_FB)
                 default: break;

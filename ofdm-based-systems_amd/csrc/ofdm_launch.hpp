@@ -167,51 +167,10 @@ struct RxArgs {
                 // 8 no equalise/demap/compare, 16 no y load
 };
 
-// ---- LDS footprints (must mirror the Carve sequences in ofdm_kernels.hpp)
-inline size_t rnd16(size_t n) { return (n + 15) & ~size_t(15); }
-inline int geo_spb(int logn, int blk = 256) {
-    const int loge = logn < 4 ? logn : 4;
-    return blk / ((1 << logn) >> loge);
-}
-inline int geo_padn(int logn) { return (1 << logn) + ((1 << logn) >> 4); }
-
-template <typename R>
-inline size_t smem_rows(int logn) {
-    const size_t c = 2 * sizeof(R);
-    const int spb = geo_spb(logn);
-    return rnd16(128 * c) + rnd16((size_t)spb * geo_padn(logn) * c) + rnd16(spb * sizeof(R)) +
-           rnd16(256 * sizeof(R));
-}
-inline int tx_slot(int logn, int cp, int L) {
+// complex elements per symbol row of the fused TX: the FFT's padded row, or the extended stream if longer
+constexpr int tx_slot(int logn, int cp, int L) {
     const int ext = (1 << logn) + cp + (L > 1 ? L - 1 : 0);
-    return geo_padn(logn) > ext ? geo_padn(logn) : ext;
-}
-// fused kernels, blk threads; tts = per-pass twiddle entries (0: the two-level table instead);
-// fast = throughput kernel (no staged bit words); row_real = rows of reals (complex128
-// throughput kernels, fft_reg_split) instead of complex rows
-template <typename R>
-inline size_t smem_tx(int logn, int blk, int lut_len, int wps, int L, int slot, int tts, bool wfir,
-                      size_t extra /* adaptive throughput kernel: per-subcarrier table */, bool fast, bool row_real) {
-    const size_t c = 2 * sizeof(R);
-    const int spb = geo_spb(logn, blk);
-    const int tls = L > 1 ? L - 1 : 1;
-    if (fast) wps = 0;
-    return rnd16((tts > 0 ? 0 : 128) * c) + rnd16((size_t)lut_len * c) + rnd16(32 * c) + rnd16(wfir ? 32 * c : 0) +
-           rnd16(kMaxLuts * sizeof(AxisInfo)) +
-           rnd16((size_t)spb * slot * (row_real ? sizeof(R) : c)) + rnd16((size_t)spb * tls * c) +
-           rnd16((size_t)spb * wps * 4) + rnd16((size_t)(blk / 64) * sizeof(double)) + rnd16((size_t)tts * c) +
-           rnd16(extra);
-}
-template <typename R>
-inline size_t smem_rx(int logn, int blk, int wps, int tts, size_t extra /* adaptive: order table */, bool fast,
-                      bool row_real) {
-    const size_t c = 2 * sizeof(R);
-    const int spb = geo_spb(logn, blk);
-    if (fast) wps = 0;
-    return rnd16((tts > 0 ? 0 : 128) * c) + rnd16(kMaxLuts * sizeof(AxisInfo)) +
-           rnd16((size_t)spb * geo_padn(logn) * (row_real ? sizeof(R) : c)) + rnd16((size_t)spb * wps * 4) +
-           rnd16((size_t)(blk / 64) * sizeof(R)) + rnd16((size_t)(blk / 64) * sizeof(unsigned long long)) +
-           rnd16((size_t)tts * c) + rnd16(extra);
+    return padded_row(1 << logn) > ext ? padded_row(1 << logn) : ext;
 }
 
 // A launcher's answer for a shape its build does not instantiate (OFDM_AB_ONLY experiment builds:
