@@ -66,9 +66,13 @@ typedef struct ofdm_desc {
        reference's QAMConstellationMapper.constellation arrays) and, per
        subcarrier, which LUT it uses.  Fixed mode: one LUT, sc_lut == NULL.
        Adaptive mode (constellation/adaptive.py:16-91): n_luts LUTs and
-       sc_lut[k] in [-1, n_luts) with -1 = inactive subcarrier (order 0). */
+       sc_lut[k] in [-1, n_luts) with -1 = inactive subcarrier (order 0).
+       Orders are powers of two up to 4096 (12 bits per subcarrier: 1024- and 4096-QAM,
+       PSK up to 4096 points).  The pool holds at most 512 entries while every order is
+       <= 256, at most 8192 once an order is larger (the reference's QAM pool 4..4096 is
+       5460).  Orders above 256 run with caller-supplied bits only (ofdm_tx / ofdm_rx). */
     int32_t n_luts;              /* 0 = no constellation in this plan, at most 8   */
-    const int32_t* lut_orders;   /* [n_luts] orders (powers of two 2..256)         */
+    const int32_t* lut_orders;   /* [n_luts] orders (powers of two 2..4096)        */
     const double* lut_pool;      /* concatenated LUTs, sum(lut_orders) complex      */
     const int32_t* sc_lut;       /* [n_fft] or NULL                                 */
     /* Channel: raw CIR (h_raw).  The plan normalises it to unit power for the
@@ -210,6 +214,10 @@ int ofdm_power(ofdm_plan_t plan, void* stream, const void* y, int64_t len, doubl
  * 64-QAM at N = 1024, adaptive square-QAM loading at N = 2048 or 256-QAM at N = 4096) run the
  * throughput kernels with the bit -- and in
  * ofdm_rx, with nr/ni and no z_out, the noise -- source swapped; other shapes the generic kernel.  n_sym = 0 is an empty call (returns 0, launches nothing).
+ * The throughput streams give each subcarrier one byte, so a plan with more than 8 bits on a
+ * subcarrier (orders above 256) takes caller bits only: bits == NULL returns OFDM_E_INVALID.
+ * A shape whose kernel layout does not fit a compute unit's LDS returns OFDM_E_INVALID naming
+ * the shape (every shape a plan accepts up to N = 4096, 32 taps, 4096-QAM fits).
  *
  * ofdm_tx: for global OFDM symbols [sym0, sym0+n_sym): map -> IFFT(ortho) (OFDM) or
  *   nothing (single carrier) -> cyclic prefix or zero guard -> linear convolution with

@@ -113,6 +113,10 @@ struct ofdm_plan_s {
     int has_const, has_channel, separable, zp, single_carrier;
     int upat;  // all LUTs use the reference's square-QAM level -> index patterns (kUPat)
     int psk_m; // the single LUT is the reference's M-PSK (LUT[gray(i)] = exp(2 pi j i / M)), M <= 32
+    // constellations above 256 points: max_bits = the most bits on one subcarrier; wide_plan = some
+    // LUT has more than 256 entries, so the fused kernels stage no LUT and use the WideAxis table
+    DevBuf wide;
+    int max_bits, wide_plan;
     size_t csize() const { return prec == OFDM_F32 ? 8 : 16; }
 };
 
@@ -136,14 +140,18 @@ int upload_cpx(DevBuf& d, const std::vector<double>& v, int prec, hipStream_t s)
 // Decision tables for one LUT.  Square-QAM LUTs as QAMConstellationMapper.generate_constellation
 // builds them (constellation/models.py:180-218) are separable: LUT[i] = lev[ki] + j lev[kq] with
 // i = (qpat[kq] << b/2) | ipat[ki], which the fused slicer needs.  Any other LUT (PSK, :356-380)
-// gets side = 0: the operator map/demap (LUT gather, brute-force NN) still work, the fused path
-// refuses the plan.
-int build_axis(const double* lut, int m, int lut_off, AxisInfo& ax) {
+// gets side = 0: map and demap gather from the LUT and search it for the nearest point, in the
+// operators and in the generic fused kernels alike.
+// Sides up to 16 fill AxisInfo's patterns (the throughput kernels' tables); every separable LUT,
+// sides 32 and 64 included, fills its WideAxis entry: the levels, the same patterns read off the LUT,
+// and their inverses for the transmitter (ofdm_device.hpp).
+int build_axis(const double* lut, int m, int lut_off, AxisInfo& ax, WideAxis& wide) {
     int b = 0;
     while ((1 << b) < m) ++b;
-    if (m < 2 || m > 256 || (1 << b) != m)
-        return fail(OFDM_E_INVALID, "constellation order must be a power of two in [2, 256]");
+    if (m < 2 || m > kMaxOrder || (1 << b) != m)
+        return fail(OFDM_E_INVALID, "constellation order must be a power of two in [2, 4096]");
     memset(&ax, 0, sizeof(ax));
+    memset(&wide, 0, sizeof(wide));
     ax.bits = b;
     ax.lut_off = lut_off;
     ax.side = 0;
@@ -172,10 +180,25 @@ int build_axis(const double* lut, int m, int lut_off, AxisInfo& ax) {
     ax.inv_step = inv_step;
     ax.side = side;
     ax.hbits = b / 2;
+    // (every level carries exactly one index pattern per axis: m = side^2 entries over side x side
+    // consistent pairs, so iset / qset are permutations of [0, side) and invert)
+    static_assert(kWideSide * kWideSide == kMaxOrder, "WideAxis holds the largest side");
     for (int k = 0; k < side; ++k) {
-        ax.ipat[k] = (uint8_t)iset[k];
-        ax.qpat[k] = (uint8_t)qset[k];
+        if (iset[k] < 0 || qset[k] < 0) return fail(OFDM_E_INVALID, "internal: incomplete level pattern");
+        if (side <= 16) {
+            ax.ipat[k] = (uint8_t)iset[k];
+            ax.qpat[k] = (uint8_t)qset[k];
+        }
+        wide.lev[k] = lev[k];
+        wide.ipat[k] = (uint8_t)iset[k];
+        wide.qpat[k] = (uint8_t)qset[k];
+        wide.inv_i[iset[k]] = (uint8_t)k;
+        wide.inv_q[qset[k]] = (uint8_t)k;
     }
+    // the transmitter's map must reproduce the LUT it replaces, bit for bit
+    for (int i = 0; i < m; ++i)
+        if (wide.lev[wide.inv_i[i & (side - 1)]] != lut[2 * i] || wide.lev[wide.inv_q[i >> (b / 2)]] != lut[2 * i + 1])
+            return fail(OFDM_E_INVALID, "internal: level tables do not reproduce the LUT");
     return OFDM_OK;
 }
 
@@ -327,12 +350,19 @@ int ofdm_plan_create(ofdm_plan_t* out, const ofdm_desc* d, void* stream) {
     // constellations
     if (p->has_const) {
         std::vector<AxisInfo> axes(d->n_luts);
-        int off = 0;
+        std::vector<WideAxis> wides(d->n_luts);
+        int off = 0, top = 0;
         for (int i = 0; i < d->n_luts; ++i) {
-            if ((rc = build_axis(d->lut_pool + 2 * off, d->lut_orders[i], off, axes[i]))) return rc;
+            // (the order is checked before the LUT is read: off stays within the caller's pool)
+            if ((rc = build_axis(d->lut_pool + 2 * off, d->lut_orders[i], off, axes[i], wides[i]))) return rc;
             off += d->lut_orders[i];
+            top = std::max(top, (int)d->lut_orders[i]);
         }
-        if (off > kMaxLut) return fail(OFDM_E_INVALID, "LUT pool too large");
+        // orders up to 256: the pool the fused kernels stage in LDS; above: never staged
+        p->wide_plan = top > 256;
+        if (off > (p->wide_plan ? kMaxPool : kMaxLut))
+            return fail(OFDM_E_INVALID, p->wide_plan ? "LUT pool too large (more than 8192 entries)"
+                                                     : "LUT pool too large (more than 512 entries with every order <= 256)");
         p->lut_len = off;
         p->n_axis = d->n_luts;
         p->separable = 1;
@@ -343,6 +373,8 @@ int ofdm_plan_create(ofdm_plan_t* out, const ofdm_desc* d, void* stream) {
         if ((rc = upload_cpx(p->lut, pool, p->prec, s))) return rc;
         if ((rc = upload(p->lut64, pool.data(), pool.size(), s))) return rc;
         if ((rc = upload(p->axis, axes.data(), axes.size(), s))) return rc;
+        if ((rc = upload(p->wide, wides.data(), wides.size(), s))) return rc;
+        p->max_bits = 0;
         if (p->adaptive) {
             std::vector<ScInfo> sc(p->n);
             std::vector<int32_t> act;
@@ -354,6 +386,7 @@ int ofdm_plan_create(ofdm_plan_t* out, const ofdm_desc* d, void* stream) {
                 sc[k].bits = (int16_t)(id < 0 ? 0 : axes[id].bits);
                 sc[k].bitoff = bit;
                 bit += sc[k].bits;
+                p->max_bits = std::max(p->max_bits, (int)sc[k].bits);
                 if (id >= 0) act.push_back(k);
             }
             if (bit == 0) return fail(OFDM_E_INVALID, "No active subcarriers (all orders are zero)");
@@ -365,6 +398,7 @@ int ofdm_plan_create(ofdm_plan_t* out, const ofdm_desc* d, void* stream) {
         } else {
             if (d->n_luts != 1) return fail(OFDM_E_INVALID, "fixed mode takes exactly one LUT");
             p->b = axes[0].bits;
+            p->max_bits = p->b;
             p->bps = p->b * p->n;
             p->n_active = p->n;
         }
@@ -591,6 +625,7 @@ int ofdm_demap(ofdm_plan_t p, void* stream, const void* z, int64_t n, uint8_t* b
     a.axis = (const AxisInfo*)p->axis.p;
     a.active = (const int32_t*)p->active.p;
     a.lut64 = (const double*)p->lut64.p;
+    a.wide = (const WideAxis*)p->wide.p;
 #define CALL(R) launch_demap<R>(a, (hipStream_t)stream)
     HIPCHK(DISPATCH(p, CALL));
 #undef CALL
@@ -621,6 +656,7 @@ int ofdm_demap_count(ofdm_plan_t p, void* stream, const void* Z, const uint8_t* 
     a.lut64 = (const double*)p->lut64.p;
     a.lut_len = p->lut_len;
     a.counters = (unsigned long long*)counters;
+    a.wide = (const WideAxis*)p->wide.p;
 #define CALL(R) launch_demap_count<R>(a, (hipStream_t)stream)
     HIPCHK(DISPATCH(p, CALL));
 #undef CALL
@@ -695,6 +731,25 @@ int ofdm_awgn(ofdm_plan_t p, void* stream, void* y, int64_t len, const double* n
     return OFDM_OK;
 }
 
+// Throughput mode (bits == NULL: Philox stream version 3) gives each element one byte of its lane
+// block, so it carries at most kMaxStreamBits bits per subcarrier; a wider order would share bits
+// between neighbouring elements.  Such a plan runs with the caller's bits only.
+static int stream_bits_ok(ofdm_plan_t p, const uint8_t* bits, const char* who) {
+    if (bits != nullptr || p->max_bits <= kMaxStreamBits) return OFDM_OK;
+    return fail(OFDM_E_INVALID, std::string(who) + ": the throughput (Philox) bit stream carries at most 8 bits per "
+                                    "subcarrier and this plan has up to " + std::to_string(p->max_bits) +
+                                    "; pass the tx bits (reference-stream mode)");
+}
+
+// The generic fused kernel's LDS layout for this shape exceeds a CU's (launcher: kLdsOverflow).
+static int lds_overflow(ofdm_plan_t p, const char* who) {
+    return fail(OFDM_E_INVALID, std::string(who) + ": the shape does not fit the LDS of a compute unit (n_fft " +
+                                    std::to_string(p->n) + ", " + (p->prec == OFDM_F32 ? "complex64" : "complex128") +
+                                    ", prefix " + std::to_string(p->cp) + ", " + std::to_string(p->L) + " taps, " +
+                                    std::to_string(p->bps) + " bits per OFDM symbol, LUT pool " +
+                                    std::to_string(p->lut_len) + ")");
+}
+
 static void fill_common(ofdm_plan_t p, TxRxCommon& c, const uint8_t* bits, uint64_t seed, int64_t sym0,
                         int64_t n_sym, int64_t total_syms_for_bits) {
     c.bits = bits;
@@ -741,10 +796,16 @@ int ofdm_tx(ofdm_plan_t p, void* stream, const uint8_t* bits, uint64_t seed, int
     if (!p || !p->has_const || p->L < 1) return fail(OFDM_E_INVALID, "ofdm_tx needs a constellation and channel taps");
     if (p->L - 1 > p->n) return fail(OFDM_E_INVALID, "fused path needs channel order <= n_fft");
     if (n_sym < 0 || sym0 < 0 || !stats) return fail(OFDM_E_INVALID, "bad argument to ofdm_tx");
+    if (int rc = stream_bits_ok(p, bits, "ofdm_tx")) return rc;
     if (n_sym == 0) return OFDM_OK;
     TxArgs a{};
     // the bits buffer covers global symbols [0, sym0 + n_sym)
     fill_common(p, a.c, bits, seed, sym0, n_sym, sym0 + n_sym);
+    if (p->wide_plan) {
+        // an order above 256: the kernel maps from the level tables and stages no LUT
+        a.wide = (const WideAxis*)p->wide.p;
+        a.c.lut_len = 0;
+    }
     a.y = y;
     a.partials = workspace(p, stream);
     if (!a.partials) return fail(OFDM_E_ALLOC, "hipMalloc failed");
@@ -756,8 +817,10 @@ int ofdm_tx(ofdm_plan_t p, void* stream, const uint8_t* bits, uint64_t seed, int
     a.flags = OFDM_ENV_FLAGS("OFDM_ABLATE_TX");
     int grid = 0;  // chosen by the launcher with the kernel (<= kMaxGrid partial records)
 #define CALL(R) launch_tx<R>(p->logn, a, &grid, (hipStream_t)stream)
-    HIPCHK(DISPATCH(p, CALL));
+    const hipError_t launch_result = DISPATCH(p, CALL);
 #undef CALL
+    if (launch_result == kLdsOverflow) return lds_overflow(p, "ofdm_tx");
+    HIPCHK(launch_result);
     HIPCHK(launch_finalize_tx(a.partials, grid, (double*)stats, (hipStream_t)stream));
     return OFDM_OK;
 }
@@ -769,6 +832,7 @@ int ofdm_rx(ofdm_plan_t p, void* stream, const void* y, const double* nr, const 
     if (!p || !p->has_const) return fail(OFDM_E_INVALID, "ofdm_rx needs a constellation");
     if (p->eq != OFDM_EQ_NONE && !p->has_channel) return fail(OFDM_E_INVALID, "plan has no channel response");
     if (n_sym < 0 || sym0 < 0 || !counters) return fail(OFDM_E_INVALID, "bad argument to ofdm_rx");
+    if (int rc = stream_bits_ok(p, bits, "ofdm_rx")) return rc;
     if (n_sym == 0) return OFDM_OK;  // an empty run (its stream has no samples and no noise power)
     if (!y || (noise_on && (!stats || total_samples <= 0))) return fail(OFDM_E_INVALID, "bad argument to ofdm_rx");
     if ((nr == nullptr) != (ni == nullptr)) return fail(OFDM_E_INVALID, "nr and ni must both be given or both NULL");
@@ -786,10 +850,13 @@ int ofdm_rx(ofdm_plan_t p, void* stream, const void* y, const double* nr, const 
     a.z_out = z_out;
     a.z_keep = z_out ? z_keep : 0;
     a.flags = OFDM_ENV_FLAGS("OFDM_ABLATE_RX");
+    a.wide = p->wide_plan ? (const WideAxis*)p->wide.p : nullptr;  // an order above 256: the wide slicer
     int grid = 0;
 #define CALL(R) launch_rx<R>(p->logn, a, &grid, (hipStream_t)stream)
-    HIPCHK(DISPATCH(p, CALL));
+    const hipError_t launch_result = DISPATCH(p, CALL);
 #undef CALL
+    if (launch_result == kLdsOverflow) return lds_overflow(p, "ofdm_rx");
+    HIPCHK(launch_result);
     return OFDM_OK;
 }
 

@@ -389,6 +389,21 @@ struct AxisInfo {
     uint8_t qpat[16];
 };
 
+// The same decomposition for sides up to 64 (orders up to 4096), in a per-plan table of its own
+// beside AxisInfo: the throughput kernels stage AxisInfo through registers and never see a side
+// above 16, so the wide patterns stay out of it.  One entry per LUT of the plan (zeros for a
+// non-separable LUT), read by the operator kernels and the generic fused kernels only.
+//   decide: index = (qpat[kq] << hbits) | ipat[ki] from the levels ki, kq the slicer finds
+//   map:    LUT[i] = lev[inv_i[i & (side - 1)]] + j lev[inv_q[i >> hbits]], exactly (build_axis)
+constexpr int kWideSide = 64;
+struct WideAxis {
+    double lev[kWideSide];      // levels, ascending
+    uint8_t ipat[kWideSide];    // level -> low index bits
+    uint8_t qpat[kWideSide];    // level -> high index bits
+    uint8_t inv_i[kWideSide];   // low index bits -> level
+    uint8_t inv_q[kWideSide];   // high index bits -> level
+};
+
 // Per-subcarrier table for adaptive bit loading.
 struct ScInfo {
     int16_t lut;     // AxisInfo index, -1 = inactive
@@ -805,8 +820,8 @@ __device__ __forceinline__ void fft_reg_split(cpx<R> (&x)[Geo<LOGN>::E], R* rb, 
 template <typename R, int LOGN>
 constexpr bool fast_tt() { return sizeof(R) == 4 || tt_size(LOGN) * 2 * (int)sizeof(R) <= 16384; }
 
-// b (<= 8) bits at bit offset o of a stream stored as 32-bit words, stream bit 32w+j
-// = bit (31-j) of word w; one word of slack after the stream.
+// b (<= 12; the 64-bit window holds any b <= 32) bits at bit offset o of a stream stored as
+// 32-bit words, stream bit 32w+j = bit (31-j) of word w; one word of slack after the stream.
 __device__ __forceinline__ uint32_t extract_w(const uint32_t* w, int o, int b) {
     const int q = o >> 5, s = o & 31;
     const uint64_t x = ((uint64_t)w[q] << 32) | (uint64_t)w[q + 1];
@@ -1460,11 +1475,23 @@ __device__ __forceinline__ uint32_t slice(cpx<R> z, const AxisInfo& a) {
     return ((uint32_t)a.qpat[kq] << a.hbits) | (uint32_t)a.ipat[ki];
 }
 
-// b (<= 8) bits at bit offset o of an MSB-first byte buffer with >= 1 byte of slack.
-__device__ __forceinline__ uint32_t extract_bits(const uint8_t* bytes, int64_t o, int b) {
+// The same decision for sides above 16 (orders 1024 and 4096, or any side <= kWideSide): the
+// rounding slicer of AxisInfo's lev0 / inv_step, the level patterns from the LUT's WideAxis entry
+// (or a copy of it: ipat / qpat point at kWideSide bytes each).
+template <typename R>
+__device__ __forceinline__ uint32_t slice_wide(cpx<R> z, const AxisInfo& a, const uint8_t* ipat, const uint8_t* qpat) {
+    const int ki = slice_axis<R>(z.re, a), kq = slice_axis<R>(z.im, a);  // clamped to [0, side - 1]
+    return ((uint32_t)qpat[kq] << a.hbits) | (uint32_t)ipat[ki];
+}
+
+// b (<= 12) bits at bit offset o of an MSB-first byte buffer of n_bytes: a window of three bytes
+// (7 + 12 = 19 bits at the worst alignment); bytes past the end read as zero.
+__device__ __forceinline__ uint32_t extract_bits(const uint8_t* bytes, int64_t n_bytes, int64_t o, int b) {
     const int64_t B = o >> 3;
-    const uint32_t w = ((uint32_t)bytes[B] << 8) | (uint32_t)bytes[B + 1];
-    return (w >> (16 - (int)(o & 7) - b)) & ((1u << b) - 1u);
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) w = (w << 8) | (B + j < n_bytes ? (uint32_t)bytes[B + j] : 0u);
+    return (w >> (24 - (int)(o & 7) - b)) & ((1u << b) - 1u);
 }
 
 }  // namespace ofdm

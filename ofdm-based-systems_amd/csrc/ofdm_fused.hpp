@@ -15,7 +15,8 @@
 // kernel for the reference's 8/32-PSK (sector decisions only); FB = 1 is the throughput kernel for adaptive
 // bit loading (per-subcarrier square-QAM orders, CAPACITY_BASED, OFDM with a cyclic prefix);
 // FB = 0 is the generic kernel (reference-mode bytes and normals, PSK, complex128, adaptive
-// SC-OFDM / zero padding).
+// SC-OFDM / zero padding); its WIDE instantiation serves plans with a constellation above 256
+// points (1024- / 4096-QAM, wide PSK): per-axis level tables instead of a LUT staged in LDS.
 #pragma once
 
 #include <algorithm>
@@ -550,10 +551,15 @@ struct TxLds {
     unsigned char* rowmem;
     uint32_t *words, *sce;
     double* red;
+    R* wlev;        // wide plan: the LUTs' scaled levels, kWideSide per LUT
+    uint8_t* winv;  // wide plan: index bits -> level, [inv_i | inv_q] of kWideSide bytes per LUT
 };
+// n_wide (generic kernel): the LUTs of a plan with an order above 256, which maps from per-axis
+// level tables (768 bytes per LUT in complex128) and stages no LUT -- lut_len is 0 then; a
+// 4096-entry complex128 LUT alone would be 64 KB beside the N = 4096 symbol row's 68 KB
 template <typename R, int LOGN, int FB, int LT, int BLK, typename CV>
 __host__ __device__ __forceinline__ constexpr TxLds<R> tx_carve(CV& cv, int lut_len, int words_per_sym, int tls,
-                                                                int slot) {
+                                                                int slot, int n_wide = 0) {
     using G = Geo<LOGN, BLK>;
     using C = cpx<R>;
     // complex128 flat and window-FIR TX: a row of reals (fft_reg_split)
@@ -574,6 +580,8 @@ __host__ __device__ __forceinline__ constexpr TxLds<R> tx_carve(CV& cv, int lut_
     // adaptive throughput kernel: per subcarrier (LUT offset << 8 | tx bit mask); unused
     // subcarriers point at a zero entry appended to the LUT pool
     m.sce = cv.template take<uint32_t>(FB == 1 ? G::N : 0);
+    m.wlev = cv.template take<R>(FB == 0 ? (size_t)n_wide * kWideSide : 0);
+    m.winv = cv.template take<uint8_t>(FB == 0 ? (size_t)n_wide * 2 * kWideSide : 0);
     return m;
 }
 // LT (throughput TX): 0 flat channel; 4 / 8 multipath with <= LT taps through the register
@@ -609,9 +617,12 @@ constexpr int tx_waves() {
 // stream samples of the previous symbol) is carried in LDS; the first symbol of a chunk
 // regenerates its predecessor's tail (one extra IFFT per chunk, L > 1 only).
 // REF: the throughput kernel fed the caller's bits (reference streams, ref_lane) -- the same body
-template <typename R, int LOGN, int FB, int LT, bool ZPW = false, bool REF = false>
+// WIDE: the generic kernel for a plan with an order above 256 (level tables instead of a staged
+// LUT), an instantiation of its own so that the generic kernel of every other plan compiles as before
+template <typename R, int LOGN, int FB, int LT, bool ZPW = false, bool REF = false, bool WIDE = false>
 __global__ __launch_bounds__((tx_block<R, FB, LOGN, LT, ZPW>()), (tx_waves<R, FB, LOGN, LT, ZPW>())) void k_tx(
     TxArgs a) {
+    static_assert(!WIDE || (FB == 0 && LT == -1 && !REF), "the wide map lives in the generic kernel");
     constexpr int BLK = tx_block<R, FB, LOGN, LT, ZPW>();
     constexpr bool WFIR = FB > 0 && LT > 0;  // register window FIR
     constexpr bool TX_NT = OFDM_TX_NT || (sizeof(R) == 8 && OFDM_TX_NT_F64);  // nontemporal y stores
@@ -647,7 +658,9 @@ __global__ __launch_bounds__((tx_block<R, FB, LOGN, LT, ZPW>()), (tx_waves<R, FB
     constexpr int HB = FB / 2, SIDE = 1 << HB;
     __shared__ R sep_s[tx_sep_static<R, FB, LT>()];
     Carve cv(ofdm_smem);
-    const TxLds<R> lds = tx_carve<R, LOGN, FB, LT, BLK>(cv, cm.lut_len, cm.words_per_sym, tls, slot);
+    // a plan with an order above 256 (WIDE): level tables instead of a staged LUT
+    const int n_wide = WIDE ? cm.n_axis : 0;
+    const TxLds<R> lds = tx_carve<R, LOGN, FB, LT, BLK>(cv, cm.lut_len, cm.words_per_sym, tls, slot, n_wide);
     C *tw = lds.tw, *lut = FB > 0 ? lut_s : lds.lut, *h = lds.h, *hsw = lds.hsw, *tails = lds.tails, *tt = lds.tt;
     AxisInfo* axis = lds.axis;
     unsigned char* rowmem = lds.rowmem;
@@ -694,6 +707,18 @@ __global__ __launch_bounds__((tx_block<R, FB, LOGN, LT, ZPW>()), (tx_waves<R, FB
         }
     }
     st_ax.store((Dwords<AxisInfo>*)axis);
+    if constexpr (WIDE) {
+        // wide plan: each LUT's levels with the 1/sqrt(N) folded in -- the staged LUT's single
+        // multiply per component, on the same values (LUT[i] = lev[ki] + j lev[kq] exactly, and the
+        // plan-precision LUT is the rounded double one) -- and its index -> level maps
+        for (int i = threadIdx.x; i < n_wide * kWideSide; i += BLK) {
+            const int l = i / kWideSide, k = i % kWideSide;
+            const WideAxis& wa = a.wide[l];
+            lds.wlev[i] = (R)wa.lev[k] * lut_scale;
+            lds.winv[2 * kWideSide * l + k] = wa.inv_i[k];
+            lds.winv[2 * kWideSide * l + kWideSide + k] = wa.inv_q[k];
+        }
+    }
     if constexpr (FB == 1) {
         if (threadIdx.x == 0) lut[cm.lut_len] = mk<R>(0, 0);
         auto code = [&](const ScInfo& sc, int off) {
@@ -775,6 +800,35 @@ __global__ __launch_bounds__((tx_block<R, FB, LOGN, LT, ZPW>()), (tx_waves<R, FB
                 });
             } else if constexpr (FB > 0) {
                 static_for<0, E>([&](auto I) { x[I] = lut[tb.template fixed<I>()]; });
+            } else if constexpr (WIDE) {
+                // a plan with an order above 256: every LUT of it maps through its
+                // level tables, x = lev[inv_i[idx & (side - 1)]] + j lev[inv_q[idx >> hbits]] -- the
+                // LUT entry's own components, scaled as the staged LUT would be; a non-separable
+                // LUT (PSK) is read from the plan's table in global memory
+#pragma unroll
+                for (int i = 0; i < E; ++i) {
+                    const int k = t + i * TPS;
+                    C v = mk<R>(0, 0);
+                    int lid = 0, b = cm.b, off = k * cm.b;
+                    if (adaptive) {
+                        const ScInfo sc = cm.sc[k];
+                        lid = sc.lut;
+                        b = sc.bits;
+                        off = sc.bitoff;
+                    }
+                    if (active && lid >= 0) {
+                        const uint32_t idx = tb.generic(i, b, off);
+                        const AxisInfo& ax = axis[lid];
+                        if (cm.nn) {
+                            v = cscale(glut[ax.lut_off + idx], lut_scale);
+                        } else {
+                            const uint8_t* inv = lds.winv + 2 * kWideSide * lid;
+                            const R* lev = lds.wlev + kWideSide * lid;
+                            v = mk<R>(lev[inv[idx & (uint32_t)(ax.side - 1)]], lev[inv[kWideSide + (idx >> ax.hbits)]]);
+                        }
+                    }
+                    x[i] = v;
+                }
             } else {
 #pragma unroll
                 for (int i = 0; i < E; ++i) {
@@ -1235,9 +1289,12 @@ struct RxLds {
     R* red;
     unsigned long long* redc;
     OP* ordt;
+    uint8_t* wpat;  // wide plan: level -> index bits, [ipat | qpat] of kWideSide bytes per LUT
 };
+// n_wide (generic kernel): the LUTs of a plan with an order above 256 (side 32 / 64 slicer tables)
 template <typename R, int LOGN, int EQ, int FB, bool MV, typename CV>
-__host__ __device__ __forceinline__ constexpr RxLds<R> rx_carve(CV& cv, int words_per_sym, int tts_all) {
+__host__ __device__ __forceinline__ constexpr RxLds<R> rx_carve(CV& cv, int words_per_sym, int tts_all,
+                                                                int n_wide = 0) {
     constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV>();
     using G = Geo<LOGN, BLK>;
     using C = cpx<R>;
@@ -1256,6 +1313,7 @@ __host__ __device__ __forceinline__ constexpr RxLds<R> rx_carve(CV& cv, int word
     // per workgroup (ZF: 1/H; MMSE: conj(H), |H|^2 recomputed from it) -- read from the plan's
     // global table, every element paid an L2 round trip with a vmcnt(0) per symbol
     m.eqt = cv.template take<C>(eq_in_lds<R, FB, LOGN, EQ>() ? G::N : 0);
+    m.wpat = cv.template take<uint8_t>(FB == 0 ? (size_t)n_wide * 2 * kWideSide : 0);
     return m;
 }
 
@@ -1263,9 +1321,12 @@ __host__ __device__ __forceinline__ constexpr RxLds<R> rx_carve(CV& cv, int word
 // MV: SC-OFDM and zero padding compiled in (run-time flags); complex128 compiles them out of the
 // cyclic-prefix OFDM kernels (rx_eq)
 // REF: the throughput kernel fed the caller's bits and normals (reference streams) -- the same body
-template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false>
+// WIDE: the generic kernel for a plan with an order above 256 (the side 32 / 64 slicer), an
+// instantiation of its own like k_tx's
+template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
 __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB, LOGN, EQ, MV>())) void k_rx(
     RxArgs a) {
+    static_assert(!WIDE || (FB == 0 && EQ == -1 && !REF), "the wide slicer lives in the generic kernel");
     constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV>();
     using G = Geo<LOGN, BLK>;
     using C = cpx<R>;
@@ -1295,7 +1356,9 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB,
     constexpr bool SPLIT = split_rows<R, FB>();  // complex128 throughput: rows of reals
     constexpr int TTS = TT ? tt_size(LOGN) : 0;
     const int tts_all = rx_tts<R, LOGN, FB>(scm);
-    const RxLds<R> lds = rx_carve<R, LOGN, EQ, FB, MV>(cv, cm.words_per_sym, tts_all);
+    // a plan with an order above 256 (WIDE): the wide slicer's level patterns in LDS
+    const int n_wide = WIDE ? cm.n_axis : 0;
+    const RxLds<R> lds = rx_carve<R, LOGN, EQ, FB, MV>(cv, cm.words_per_sym, tts_all, n_wide);
     C *tw = lds.tw, *tt = lds.tt, *eqt = lds.eqt;
     AxisInfo* axis = lds.axis;
     unsigned char* rowmem = lds.rowmem;
@@ -1335,6 +1398,13 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB,
     st_tt.store(tt);
     if constexpr (EQ_LDS) st_eq.store(eqt);
     st_ax.store((Dwords<AxisInfo>*)axis);
+    if constexpr (WIDE) {
+        for (int i = threadIdx.x; i < n_wide * kWideSide; i += BLK) {
+            const int l = i / kWideSide, k = i % kWideSide;
+            lds.wpat[2 * kWideSide * l + k] = a.wide[l].ipat[k];
+            lds.wpat[2 * kWideSide * l + kWideSide + k] = a.wide[l].qpat[k];
+        }
+    }
     if constexpr (FB == 1 && sizeof(R) == 8) {
         if (threadIdx.x < 8) {
             OrderParams64 o = OrderParams64::make(0.0, 0.0, 0.0, 0u);  // unused subcarrier: level 0, no bits
@@ -1415,7 +1485,8 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB,
         // The reference's 4/16-PSK (psk_m > 0) decide by sector and have no axis tables.
         if (cm.psk_m == 0) pslicer.load(axis[0], scm ? cm.scale * cm.scale : cm.scale);
     } else if (!adaptive) {
-        slicer.load(axis[0]);
+        // (its nibble patterns hold sides <= 16; a wide plan decides by slice_wide)
+        if constexpr (!WIDE) slicer.load(axis[0]);
     }
 
     const bool array_noise = (FB == 0 || REF) && a.nr != nullptr && noise;
@@ -1713,11 +1784,21 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB,
                         off = sc.bitoff;
                         // PSK orders (constellation/adaptive.py:130-265 with the PSK base mapper):
                         // the nearest point of the subcarrier's own LUT
-                        ridx = nn ? nn_decide<R>(v, cm, axis[sc.lut].lut_off, 1 << sc.bits) : slice<R>(v, axis[sc.lut]);
+                        // (a plan with an order above 256: every LUT of it through the wide tables)
+                        if constexpr (WIDE)
+                            ridx = nn ? nn_decide<R>(v, cm, axis[sc.lut].lut_off, 1 << sc.bits)
+                                      : slice_wide<R>(v, axis[sc.lut], lds.wpat + 2 * kWideSide * sc.lut,
+                                                      lds.wpat + 2 * kWideSide * sc.lut + kWideSide);
+                        else
+                            ridx = nn ? nn_decide<R>(v, cm, axis[sc.lut].lut_off, 1 << sc.bits) : slice<R>(v, axis[sc.lut]);
                     } else {
                         b = cm.b;
                         off = k * b;
-                        ridx = nn ? nn_decide<R>(v, cm, 0, cm.lut_len) : slicer(v);
+                        if constexpr (WIDE)
+                            ridx = nn ? nn_decide<R>(v, cm, 0, cm.lut_len)
+                                      : slice_wide<R>(v, axis[0], lds.wpat, lds.wpat + kWideSide);
+                        else
+                            ridx = nn ? nn_decide<R>(v, cm, 0, cm.lut_len) : slicer(v);
                     }
                     uint32_t d = ridx ^ tb.generic(i, b, off);
                     ses += d != 0u;

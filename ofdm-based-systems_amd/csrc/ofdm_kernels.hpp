@@ -194,15 +194,9 @@ __global__ __launch_bounds__(kBlock) void k_map(MapArgs a) {
             b = a.b;
             lutoff = 0;
         }
-        // bits past the input read as zero (encode zero-pads, constellation/models.py:235-237)
-        uint32_t idx = 0;
-        for (int i = 0; i < b; ++i) {
-            const int64_t p = o + i;
-            const int64_t B = p >> 3;
-            const uint32_t bit = B < a.n_bytes ? (a.bytes[B] >> (7 - (int)(p & 7))) & 1u : 0u;
-            idx = (idx << 1) | bit;
-        }
-        out[e] = lut[lutoff + idx];
+        // bits past the input read as zero (encode zero-pads, constellation/models.py:235-237);
+        // b <= 12: a three-byte window at any alignment
+        out[e] = lut[lutoff + extract_bits(a.bytes, a.n_bytes, o, b)];
     }
 }
 
@@ -257,22 +251,26 @@ __global__ __launch_bounds__(kBlock) void k_demap(DemapArgs a) {
                 }
                 if (e != cur_e) {
                     cur_e = e;
-                    int lutoff, m;
+                    int lid, m;
                     if (a.adaptive) {
                         const int k = (int)(e % a.n_fft);
                         const ScInfo sc = a.sc[k];
-                        lutoff = a.axis[sc.lut].lut_off;
+                        lid = sc.lut;
                         m = 1 << sc.bits;
                         cur_b = sc.bits;
                         cur_o = (e / a.n_fft) * a.bps + sc.bitoff;
                     } else {
-                        lutoff = 0;
+                        lid = 0;
                         m = 1 << a.b;
                         cur_b = a.b;
                         cur_o = e * a.b;
                     }
                     const C v = z[e];
-                    cur_idx = (uint32_t)nn_index((double)v.re, (double)v.im, a.lut64 + 2 * lutoff, m);
+                    const AxisInfo& ax = a.axis[lid];
+                    // a separable LUT of side 32 / 64 (1024- / 4096-QAM): the per-axis slicer through
+                    // the wide tables, not a search over thousands of points per byte
+                    cur_idx = ax.side > 16 ? slice_wide<R>(v, ax, a.wide[lid].ipat, a.wide[lid].qpat)
+                                           : (uint32_t)nn_index((double)v.re, (double)v.im, a.lut64 + 2 * ax.lut_off, m);
                 }
                 const int pos = (int)(p - cur_o);
                 bit = (cur_idx >> (cur_b - 1 - pos)) & 1u;
@@ -315,15 +313,13 @@ __global__ __launch_bounds__(kBlock) void k_demap_count(DemapCountArgs a) {
         }
         const C v = z[e];
         const AxisInfo& ax = a.axis[lut];
-        const uint32_t ridx = a.separable ? slice<R>(v, ax)
-                                          : (uint32_t)nn_index((double)v.re, (double)v.im, a.lut64 + 2 * ax.lut_off, 1 << b);
+        // (side > 16: 1024- / 4096-QAM, whose level patterns live in the plan's WideAxis table)
+        const uint32_t ridx =
+            !a.separable ? (uint32_t)nn_index((double)v.re, (double)v.im, a.lut64 + 2 * ax.lut_off, 1 << b)
+            : ax.side > 16 ? slice_wide<R>(v, ax, a.wide[lut].ipat, a.wide[lut].qpat)
+                           : slice<R>(v, ax);
         const int64_t o = s * (int64_t)a.bps + off;
-        uint32_t t = 0;
-        for (int i = 0; i < b; ++i) {
-            const int64_t p = o + i;
-            const int64_t B = p >> 3;
-            t = (t << 1) | (B < a.n_tx_bytes ? (a.tx[B] >> (7 - (int)(p & 7))) & 1u : 0u);
-        }
+        const uint32_t t = extract_bits(a.tx, a.n_tx_bytes, o, b);  // b <= 12: three bytes, zeros past the end
         uint32_t d = ridx ^ t;
         se += d != 0u;
         const int64_t nvb = a.n_valid_bits - o;

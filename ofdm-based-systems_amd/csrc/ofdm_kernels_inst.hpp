@@ -171,18 +171,24 @@ static inline int fused_grid(int64_t want, int resident) {
     return clamp_grid(want);
 }
 
-template <typename R, int LOGN, int FB, int LT, bool ZPW = false, bool REF = false>
+// WIDE: the generic kernel's instantiation for a plan with an order above 256 (a.wide set)
+template <typename R, int LOGN, int FB, int LT, bool ZPW = false, bool REF = false, bool WIDE = false>
 static hipError_t tx_launch(const TxArgs& a0, int* grid, hipStream_t s) {
     constexpr int BLK = tx_block<R, FB, LOGN, LT, ZPW>();
+    if ((a0.wide != nullptr) != WIDE) return hipErrorInvalidValue;  // (tx_one sends a wide plan here, nothing else)
     TxArgs a = a0;
     a.slot = tx_row_slot<R, LOGN, FB, LT>(a.slot, a.c.cp);
     CarveSize lds;
-    tx_carve<R, LOGN, FB, LT, BLK>(lds, a.c.lut_len, a.c.words_per_sym, tx_tails(a.L), a.slot);
+    tx_carve<R, LOGN, FB, LT, BLK>(lds, a.c.lut_len, a.c.words_per_sym, tx_tails(a.L), a.slot,
+                                   WIDE ? a.c.n_axis : 0);  // (a wide plan's level tables)
     const size_t sm = lds.bytes;
     if constexpr (FB > 0) {
         if (sm + tx_static_lds<R, FB, LT>() > kLdsPerCu) return tx_launch<R, LOGN, 0, -1>(a0, grid, s);
+    } else {
+        // the generic kernel is the last resort: a shape it cannot hold is refused, not launched
+        if (sm + tx_static_lds<R, FB, LT>() > kLdsPerCu) return kLdsOverflow;
     }
-    auto fn = k_tx<R, LOGN, FB, LT, ZPW, REF>;
+    auto fn = k_tx<R, LOGN, FB, LT, ZPW, REF, WIDE>;
     hipError_t e = set_smem(fn, sm);
     if (e != hipSuccess) return e;
     const int resident = resident_blocks(fn, BLK, sm);
@@ -223,6 +229,9 @@ static hipError_t tx_fast(const TxArgs& a, int* grid, hipStream_t s) {
 // 64-QAM at N = 1024 (configs b, c) and 256-QAM at N = 4096 (config e), adaptive square-QAM loading
 // at N = 2048 (config d, FB = 1), flat or <= 8-tap channels within the window FIR's reach.
 // Everything else with caller bits takes the generic kernel.
+// Orders above 256 (1024- / 4096-QAM, wide PSK) always do, by the rules below as they stand: upat is
+// false for a side above 16 (adaptive_fast), ref_shape asks for b = FB <= 8, and the FB switch has no
+// case above 8 -- and the ABI refuses such a plan without caller bits before any launcher runs.
 template <typename R, int LOGN>
 constexpr int ref_fb() { return sizeof(R) == 8 ? (LOGN == 10 ? 6 : LOGN == 11 ? 1 : LOGN == 12 ? 8 : 0) : 0; }
 
@@ -264,6 +273,8 @@ static hipError_t tx_one(const TxArgs& a, int* grid, hipStream_t s) {
 #undef OFDM_TX_FB
         }
     }
+    // the generic kernel; a plan with an order above 256 its WIDE instantiation
+    if (a.wide != nullptr) return tx_launch<R, LOGN, 0, -1, false, false, true>(a, grid, s);
     return tx_launch<R, LOGN, 0, -1>(a, grid, s);
 }
 
@@ -280,16 +291,19 @@ hipError_t launch_tx(int logn, const TxArgs& a, int* grid, hipStream_t s) {
 #undef OFDM_TX_CASE
 }
 
-template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false>
+template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
 static hipError_t rx_launch(const RxArgs& a, int* grid, hipStream_t s) {
     constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV>();
+    if ((a.wide != nullptr) != WIDE) return hipErrorInvalidValue;  // (as tx_launch)
     CarveSize lds;
-    rx_carve<R, LOGN, EQ, FB, MV>(lds, a.c.words_per_sym, rx_tts<R, LOGN, FB>(a.c.scm));
+    rx_carve<R, LOGN, EQ, FB, MV>(lds, a.c.words_per_sym, rx_tts<R, LOGN, FB>(a.c.scm), WIDE ? a.c.n_axis : 0);
     const size_t sm = lds.bytes;
     if constexpr (FB > 0) {
         if (sm + rx_static_lds<R, FB>() > kLdsPerCu) return rx_launch<R, LOGN, -1, 0, true>(a, grid, s);
+    } else {
+        if (sm + rx_static_lds<R, FB>() > kLdsPerCu) return kLdsOverflow;  // (as tx_launch)
     }
-    auto fn = k_rx<R, LOGN, EQ, FB, MV, REF>;
+    auto fn = k_rx<R, LOGN, EQ, FB, MV, REF, WIDE>;
     hipError_t e = set_smem(fn, sm);
     if (e != hipSuccess) return e;
     const int64_t want = (a.c.n_sym + Geo<LOGN, BLK>::SPB - 1) / Geo<LOGN, BLK>::SPB;
@@ -341,6 +355,7 @@ static hipError_t rx_one(const RxArgs& a, int* grid, hipStream_t s) {
 #undef OFDM_RX_FB
         }
     }
+    if (a.wide != nullptr) return rx_launch<R, LOGN, -1, 0, true, false, true>(a, grid, s);  // (as tx_one)
     return rx_launch<R, LOGN, -1, 0, true>(a, grid, s);
 }
 

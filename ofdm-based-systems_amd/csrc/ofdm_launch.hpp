@@ -24,7 +24,17 @@ constexpr int kMaxGrid = 4096;  // partial-sum workspace rows
 constexpr int kTxFields = 4;
 constexpr int kMaxTaps = 32;
 constexpr int kWinTaps = 8;  // taps of the register-window FIR (LT = 4 / 8)
+// LUT pool of a plan whose orders are all <= 256: the pool the fused kernels stage in LDS (the
+// generic kernel in dynamic LDS, the adaptive throughput kernel in static LDS)
 constexpr int kMaxLut = 512;
+// largest constellation order (12 bits per subcarrier), and the pool of a plan that has an order
+// above 256: such a plan's LUTs are never staged (WideAxis, ofdm_device.hpp), so the pool is bounded
+// only by the plan's tables.  The reference's QAM pool 4 + 16 + ... + 4096 is 5460 entries, its
+// eight largest PSK orders 32 + ... + 4096 are 8160.
+constexpr int kMaxOrder = 4096;
+constexpr int kMaxPool = 8192;
+// bits per subcarrier the throughput (Philox) stream carries: one byte of the lane block per element
+constexpr int kMaxStreamBits = 8;
 // LUTs per plan: adaptive loading uses one per distinct order (PSK: 2 .. 256, eight orders)
 constexpr int kMaxLuts = 8;
 
@@ -69,6 +79,7 @@ struct DemapArgs {
     const AxisInfo* axis;
     const int32_t* active;
     const double* lut64;
+    const WideAxis* wide;  // per LUT, for sides above 16
 };
 
 struct DemapCountArgs {
@@ -81,6 +92,7 @@ struct DemapCountArgs {
     const double* lut64;
     int lut_len;
     unsigned long long* counters;
+    const WideAxis* wide;  // per LUT, for sides above 16
 };
 
 struct ConvArgs {
@@ -148,6 +160,9 @@ struct TxArgs {
     // complex128 window FIR: the first kWinTaps taps in Gauss form (re, re + im, im - re), read
     // from the kernel arguments into scalar registers (the taps are wave-uniform)
     double gtap[3][kWinTaps];
+    // a plan with an order above 256 (generic kernel only): its per-LUT level tables; the kernel maps
+    // through them (non-separable LUTs: from the plan's global LUT) and stages no LUT (c.lut_len = 0)
+    const WideAxis* wide;
 };
 
 struct RxArgs {
@@ -165,6 +180,7 @@ struct RxArgs {
     int64_t z_keep;
     int flags;  // diagnostic ablation (OFDM_ABLATION builds, OFDM_ABLATE_RX): 1 no noise, 2 no FFT, 4 no bit staging,
                 // 8 no equalise/demap/compare, 16 no y load
+    const WideAxis* wide;  // a plan with an order above 256 (generic kernel only): per-LUT level patterns
 };
 
 // complex elements per symbol row of the fused TX: the FFT's padded row, or the extended stream if longer
@@ -182,6 +198,9 @@ constexpr bool kAbOnly = true;
 constexpr bool kAbOnly = false;
 #endif
 constexpr hipError_t kNotInBuild = hipErrorNotSupported;  // (only ever meant so when kAbOnly)
+// A fused launcher's answer for a shape whose LDS layout does not fit a CU (kLdsPerCu): nothing was
+// launched; the ABI reports it as OFDM_E_INVALID naming the shape.
+constexpr hipError_t kLdsOverflow = hipErrorLaunchOutOfResources;
 
 // ---- launchers (instantiated for float and double in ofdm_kernels_f{32,64}.hip)
 template <typename R>
