@@ -44,12 +44,14 @@ int fail(int code, const std::string& msg) {
     } while (0)
 
 // H[k] = sum_l h_raw[l] exp(-2 pi i (l k mod N) / N): np.fft.fft(h_raw, N)
-// (simulation/models.py:264) as a direct L-tap DFT in double precision.
+// (simulation/models.py:264) as a direct L-tap DFT in double precision.  np.fft.fft(x, n) crops an
+// input longer than n, so taps l >= N (a plan allows L = N + 1) do not enter H -- they are not
+// aliased onto l mod N.
 __global__ void k_taps_dft(const double* h, int L, int N, double* H) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= N) return;
     double re = 0, im = 0;
-    for (int l = 0; l < L; ++l) {
+    for (int l = 0; l < min(L, N); ++l) {
         const long long m = ((long long)l * k) % N;
         double s, c;
         sincospi(-2.0 * (double)m / (double)N, &s, &c);

@@ -135,9 +135,10 @@ IDS = [_id(c) for c in CASES]
 
 
 def setup(N, M, ch, eq, prec, var=None, snr=None):
-    """Engine of a case; returns (engine, CIR, cp, keyword arguments for P.run_philox)."""
+    """Engine of a case; returns (engine, CIR, cp, keyword arguments for P.run_philox).
+    ch: a channel fixture's name, or the impulse response itself."""
     var = dict(var or {})
-    h = channel(ch)
+    h = channel(ch) if isinstance(ch, str) else np.asarray(ch, np.complex128)
     cp = var.pop("cp", len(h) - 1)
     sc = None
     ser = var.pop("ser", 1e-3)
@@ -157,13 +158,20 @@ def setup(N, M, ch, eq, prec, var=None, snr=None):
 
 @pytest.mark.parametrize("N,M,ch,eq,S,snr,prec,var", CASES, ids=IDS)
 def test_tx_samples_match_oracle(gpu, N, M, ch, eq, S, snr, prec, var):
+    check_tx_samples(N, M, ch, eq, S, snr, prec, var)
+
+
+def check_tx_samples(N, M, ch, eq, S, snr, prec, var, ref=None):
+    """The transmitter's samples and statistics against the oracle's (ref: its noiseless run of this
+    case, when the caller already has it -- it does not depend on the precision); returns that run."""
     eng, h, cp, var = setup(N, M, ch, eq, prec, var, snr)
     seed = 1234
     y = torch.empty((S, eng.ystride), dtype=eng.cdtype, device="cuda")
     stats = new_stats("cuda")
     eng.tx(eng.stream(), None, seed, 0, S, y, stats)
     torch.cuda.synchronize()
-    ref = P.run_philox(seed, S, N, M, h, cp, eq, snr, noise_on=False, **var)
+    if ref is None:
+        ref = P.run_philox(seed, S, N, M, h, cp, eq, snr, noise_on=False, **var)
     got = y.cpu().numpy()
     rms = np.sqrt(np.mean(np.abs(ref.y) ** 2))
     tol = 1e-4 if prec == B.OFDM_F32 else 1e-12
@@ -174,6 +182,7 @@ def test_tx_samples_match_oracle(gpu, N, M, ch, eq, S, snr, prec, var):
     assert st[0] == pytest.approx(ref.power_sum, rel=rt)
     assert st[1] == pytest.approx(ref.x_power_sum, rel=rt)
     assert st[2] == pytest.approx(ref.x_peak, rel=rt)
+    return ref
 
 
 def gpu_radius(words: np.ndarray) -> np.ndarray:
@@ -218,7 +227,11 @@ def tx_deviation(eng, seed, S):
 
 @pytest.mark.parametrize("N,M,ch,eq,S,snr,prec,var", CASES, ids=IDS)
 def test_error_counts_match_oracle(gpu, N, M, ch, eq, S, snr, prec, var):
-    case_id = _id((N, M, ch, eq, S, snr, prec, var))
+    check_error_counts(_id((N, M, ch, eq, S, snr, prec, var)), N, M, ch, eq, S, snr, prec, var)
+
+
+def check_error_counts(case_id, N, M, ch, eq, S, snr, prec, var):
+    """A run's error counts against the oracle's decision brackets on the same bits and noise."""
     eng, h, cp, var = setup(N, M, ch, eq, prec, var, snr)
     seed = 77
     res = eng.run(S, snr, seed=seed)
@@ -245,6 +258,7 @@ def test_error_counts_match_oracle(gpu, N, M, ch, eq, S, snr, prec, var):
     if wmax is not None:
         assert be_hi - be_lo <= wmax and se_hi - se_lo <= wmax, (ref.bracket, wmax)
     assert res.power_sum == pytest.approx(ref.power_sum, rel=1e-5 if prec == B.OFDM_F32 else 1e-12)
+    return res, ref
 
 
 def test_gpu_noise_radius_within_its_bound(gpu):
