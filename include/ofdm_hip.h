@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define OFDM_ABI_VERSION 5
+#define OFDM_ABI_VERSION 6
 
 #define OFDM_OK 0
 #define OFDM_E_INVALID (-1)  /* bad argument / unsupported shape          */
@@ -248,6 +248,36 @@ int ofdm_rx(ofdm_plan_t plan, void* stream, const void* y, const double* nr, con
             uint64_t seed, const ofdm_stats* stats, int64_t total_samples, double snr_db,
             int32_t noise_on, const uint8_t* bits, int64_t sym0, int64_t n_sym,
             int64_t n_valid_bits, uint64_t* counters, void* z_out, int64_t z_keep);
+
+/*
+ * ofdm_rx with a per-subcarrier profile of the run (ABI 6).  The reference returns every equalised
+ * symbol as received_symbols and compares the decoded bits against the transmitted ones
+ * (simulation/models.py:596-618); its per-subcarrier views are computed from that array.  Here the
+ * per-subcarrier sums are accumulated on the device, where the decisions are made.
+ *
+ * profile: device int64[5][N], zeroed by the caller and accumulated by every call of a run (of
+ * every batch; the records of several ranks add as integers).  Row r of subcarrier k:
+ *   0  bit errors:    subcarrier k's share of counters[0] (the same n_valid_bits and adaptive
+ *                     partial-byte masking); sum over k = this call's counters[0] increment, exactly
+ *   1  symbol errors: its share of counters[1], the same invariant
+ *   2, 3  error-vector power sum over the symbols of min(|z - c|^2, 2^20) as 32-bit limbs in units of
+ *                     2^-40, the format of ofdm_stats.power_fx: value = row3 2^-8 + row2 2^-40 after
+ *                     row3 += row2 >> 32, row2 &= 2^32 - 1.  z is the equalised symbol as z_out
+ *                     reports it (MMSE scale applied, after the IFFT for single carrier), c the
+ *                     transmitted point of the plan's LUT; each sample is rounded once to 2^-40
+ *   4  clipped:       samples whose |z - c|^2 reached the cap 2^20 or was not finite (ZF on a null bin)
+ * Inactive subcarriers (adaptive order 0) stay zero in every row.  Integer accumulation throughout:
+ * the record is identical for any batching, grid and rank count.
+ * Kernels: the complex128 bench shapes (cyclic-prefix OFDM; 64-QAM at N = 1024, adaptive square-QAM
+ * loading at N = 2048, 256-QAM at N = 4096) with throughput streams (bits == NULL, nr == NULL) and no
+ * z_out run their throughput receiver's k_rx_prof instantiation; every other call the generic
+ * kernel's.  Everything else -- arguments, counters, z_out / z_keep -- is ofdm_rx's.
+ */
+int ofdm_rx_profile(ofdm_plan_t plan, void* stream, const void* y, const double* nr, const double* ni,
+                    uint64_t seed, const ofdm_stats* stats, int64_t total_samples, double snr_db,
+                    int32_t noise_on, const uint8_t* bits, int64_t sym0, int64_t n_sym,
+                    int64_t n_valid_bits, uint64_t* counters, void* z_out, int64_t z_keep,
+                    int64_t* profile);
 
 #ifdef __cplusplus
 }

@@ -827,16 +827,18 @@ int ofdm_tx(ofdm_plan_t p, void* stream, const uint8_t* bits, uint64_t seed, int
     return OFDM_OK;
 }
 
-int ofdm_rx(ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni, uint64_t seed,
-            const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on, const uint8_t* bits,
-            int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters, void* z_out,
-            int64_t z_keep) {
-    if (!p || !p->has_const) return fail(OFDM_E_INVALID, "ofdm_rx needs a constellation");
+// ofdm_rx and ofdm_rx_profile (who; profile: the record, or null for ofdm_rx)
+static int rx_call(const char* who, ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni,
+                   uint64_t seed, const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on,
+                   const uint8_t* bits, int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters,
+                   void* z_out, int64_t z_keep, int64_t* profile) {
+    const std::string bad = std::string("bad argument to ") + who;
+    if (!p || !p->has_const) return fail(OFDM_E_INVALID, std::string(who) + " needs a constellation");
     if (p->eq != OFDM_EQ_NONE && !p->has_channel) return fail(OFDM_E_INVALID, "plan has no channel response");
-    if (n_sym < 0 || sym0 < 0 || !counters) return fail(OFDM_E_INVALID, "bad argument to ofdm_rx");
-    if (int rc = stream_bits_ok(p, bits, "ofdm_rx")) return rc;
+    if (n_sym < 0 || sym0 < 0 || !counters) return fail(OFDM_E_INVALID, bad);
+    if (int rc = stream_bits_ok(p, bits, who)) return rc;
     if (n_sym == 0) return OFDM_OK;  // an empty run (its stream has no samples and no noise power)
-    if (!y || (noise_on && (!stats || total_samples <= 0))) return fail(OFDM_E_INVALID, "bad argument to ofdm_rx");
+    if (!y || (noise_on && (!stats || total_samples <= 0))) return fail(OFDM_E_INVALID, bad);
     if ((nr == nullptr) != (ni == nullptr)) return fail(OFDM_E_INVALID, "nr and ni must both be given or both NULL");
     RxArgs a{};
     fill_common(p, a.c, bits, seed, sym0, n_sym, sym0 + n_sym);
@@ -853,13 +855,32 @@ int ofdm_rx(ofdm_plan_t p, void* stream, const void* y, const double* nr, const 
     a.z_keep = z_out ? z_keep : 0;
     a.flags = OFDM_ENV_FLAGS("OFDM_ABLATE_RX");
     a.wide = p->wide_plan ? (const WideAxis*)p->wide.p : nullptr;  // an order above 256: the wide slicer
+    a.profile = profile;
     int grid = 0;
-#define CALL(R) launch_rx<R>(p->logn, a, &grid, (hipStream_t)stream)
+#define CALL(R) (profile ? launch_rx_prof<R>(p->logn, a, &grid, (hipStream_t)stream) \
+                         : launch_rx<R>(p->logn, a, &grid, (hipStream_t)stream))
     const hipError_t launch_result = DISPATCH(p, CALL);
 #undef CALL
-    if (launch_result == kLdsOverflow) return lds_overflow(p, "ofdm_rx");
+    if (launch_result == kLdsOverflow) return lds_overflow(p, who);
     HIPCHK(launch_result);
     return OFDM_OK;
+}
+
+int ofdm_rx(ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni, uint64_t seed,
+            const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on, const uint8_t* bits,
+            int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters, void* z_out,
+            int64_t z_keep) {
+    return rx_call("ofdm_rx", p, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0, n_sym,
+                   n_valid_bits, counters, z_out, z_keep, nullptr);
+}
+
+int ofdm_rx_profile(ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni, uint64_t seed,
+                    const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on,
+                    const uint8_t* bits, int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters,
+                    void* z_out, int64_t z_keep, int64_t* profile) {
+    if (!profile) return fail(OFDM_E_INVALID, "ofdm_rx_profile needs a profile record");
+    return rx_call("ofdm_rx_profile", p, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0,
+                   n_sym, n_valid_bits, counters, z_out, z_keep, profile);
 }
 
 }  // extern "C"

@@ -181,6 +181,8 @@ struct RxArgs {
     int flags;  // diagnostic ablation (OFDM_ABLATION builds, OFDM_ABLATE_RX): 1 no noise, 2 no FFT, 4 no bit staging,
                 // 8 no equalise/demap/compare, 16 no y load
     const WideAxis* wide;  // a plan with an order above 256 (generic kernel only): per-LUT level patterns
+    // ofdm_rx_profile: the run's per-subcarrier record, int64[5][N] (ofdm_hip.h); read by k_rx_prof only
+    int64_t* profile;
 };
 
 // complex elements per symbol row of the fused TX: the FFT's padded row, or the extended stream if longer
@@ -224,6 +226,9 @@ template <typename R>
 hipError_t launch_tx(int logn, const TxArgs& a, int* grid, hipStream_t s);
 template <typename R>
 hipError_t launch_rx(int logn, const RxArgs& a, int* grid, hipStream_t s);
+// the receiver with the per-subcarrier profile (a.profile set; ofdm_prof_inst.hpp)
+template <typename R>
+hipError_t launch_rx_prof(int logn, const RxArgs& a, int* grid, hipStream_t s);
 
 hipError_t launch_finalize(const double* partials, int nblocks, int nfields, int max_mask,
                            double* stats, hipStream_t s);

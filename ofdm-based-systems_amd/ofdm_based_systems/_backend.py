@@ -26,12 +26,16 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib",
                                                if os.environ.get("OFDM_LIB_VARIANT") else ""))
 # ABI 5: throughput-mode stream version 3 (the noise radius takes the whole lane word, the phase
 # its own word per four samples; csrc/ofdm_device.hpp "throughput-mode streams")
-ABI_VERSION = 5
+# ABI 6: ofdm_rx_profile (the fused receiver with a per-subcarrier error / EVM record)
+ABI_VERSION = 6
 
 OFDM_F32, OFDM_F64 = 0, 1
 # ofdm_stats (include/ofdm_hip.h): power_sum, x_power_sum, x_peak (double), power_fx[2] (int64)
 STATS_WORDS = 5
 FX_HI, FX_LO = 2.0 ** -8, 2.0 ** -40
+# ofdm_rx_profile's record: int64[PROFILE_ROWS][N] -- bit errors, symbol errors, the two limbs of
+# the error-vector power (the power_fx format), clipped samples
+PROFILE_ROWS = 5
 EQ_NONE, EQ_ZF, EQ_MMSE = 0, 1, 2
 PREFIX_CYCLIC, PREFIX_ZERO = 0, 1
 MOD_OFDM, MOD_SC = 0, 1
@@ -104,6 +108,8 @@ SIGNATURES = {
     "ofdm_tx": (ctypes.c_int, [_VP, _VP, _VP, _U64, _I64, _I64, _VP, _VP]),
     "ofdm_rx": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _I64, _F64, _I32, _VP, _I64, _I64,
                                _I64, _VP, _VP, _I64]),
+    "ofdm_rx_profile": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _I64, _F64, _I32, _VP, _I64, _I64,
+                                       _I64, _VP, _VP, _I64, _VP]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -22,7 +22,8 @@ Bit / noise sources:
 Multi-GPU: symbols [r*S/R, (r+1)*S/R) go to rank r; the only exchanges are one
 all-gather of the 40-byte ofdm_stats record per rank (the AWGN power is a whole-stream
 mean, noise/models.py:14, kept as an exact fixed-point sum so that sigma does not depend
-on the rank count) and one all-reduce of the two u64 counters.
+on the rank count) and one all-reduce of the two u64 counters -- with ``profile=True`` of the
+counters and the per-subcarrier record behind them (integers: the sum is exact).
 """
 
 from __future__ import annotations
@@ -40,6 +41,42 @@ DEFAULT_Y_BUDGET = 64 << 30  # bytes of kept channel samples held at once per GP
 
 
 @dataclass
+class SubcarrierProfile:
+    """Per-subcarrier results of a whole run (``ofdm_rx_profile``, include/ofdm_hip.h), accumulated
+    on the device in integers: identical for any batching and rank count."""
+    bit_errors: np.ndarray           # int64 [N]; sums to LinkStats.bit_errors
+    symbol_errors: np.ndarray        # int64 [N]; sums to LinkStats.symbol_errors
+    clipped: np.ndarray              # int64 [N]: samples whose |z - c|^2 reached 2^20 or was not finite
+    error_power: np.ndarray          # float64 [N]: sum over the symbols of min(|z - c|^2, 2^20)
+    error_power_fx: np.ndarray       # int64 [2][N]: error_power's exact 32-bit limbs, units of 2^-40
+    n_symbols: int                   # OFDM symbols of the run
+    bits_per_subcarrier: np.ndarray  # int64 [N]; 0 = inactive (every row zero there)
+
+    @property
+    def ber(self) -> np.ndarray:
+        """Bit error rate per subcarrier (NaN where inactive).  The denominator is every bit the
+        subcarrier carried; an adaptive run's trailing partial byte is not compared (valid_bits)."""
+        den = (self.n_symbols * self.bits_per_subcarrier).astype(np.float64)
+        return np.divide(self.bit_errors, den, out=np.full(len(den), np.nan), where=den > 0)
+
+    @property
+    def ser(self) -> np.ndarray:
+        """Symbol error rate per subcarrier (NaN where inactive)."""
+        den = np.where(self.bits_per_subcarrier > 0, float(self.n_symbols), 0.0)
+        return np.divide(self.symbol_errors, den, out=np.full(len(den), np.nan), where=den > 0)
+
+    @property
+    def mer_db(self) -> np.ndarray:
+        """Modulation error ratio -10 log10(error_power / n_symbols) in dB: the LUTs have unit
+        power, so this is the post-equaliser SNR of the subcarrier (NaN where inactive)."""
+        out = np.full(len(self.error_power), np.nan)
+        act = (self.bits_per_subcarrier > 0) & (self.n_symbols > 0)
+        with np.errstate(divide="ignore"):
+            out[act] = -10.0 * np.log10(self.error_power[act] / max(self.n_symbols, 1))
+        return out
+
+
+@dataclass
 class LinkStats:
     bit_errors: int
     symbol_errors: int
@@ -51,6 +88,7 @@ class LinkStats:
     papr_db: float
     received: Optional[np.ndarray] = None
     timings: dict = field(default_factory=dict)
+    profile: Optional[SubcarrierProfile] = None  # run(..., profile=True)
 
 
 def new_stats(dev) -> torch.Tensor:
@@ -74,6 +112,22 @@ def combine_stats(stats: torch.Tensor, parts) -> None:
     stats[0] = l1.to(torch.float64) * B.FX_HI + l0.to(torch.float64) * B.FX_LO
     stats[1] = g[:, 1].sum()
     stats[2] = g[:, 2].max()
+
+
+def combine_profile(parts) -> np.ndarray:
+    """Add profile records (int64 [5][N] each: a rank's, or a batch's) and normalise the
+    error-power limbs as combine_stats does: rows 2 / 3 are 32-bit limbs in units of 2^-40
+    (ofdm_stats.power_fx's format) that every workgroup adds to without carrying, so row 3 takes
+    row 2's carry and row 2 keeps its low 32 bits.  Integer arithmetic: exact in any order."""
+    rec = np.sum([np.asarray(p, dtype=np.int64) for p in parts], axis=0, dtype=np.int64)
+    rec[3] += rec[2] >> 32
+    rec[2] &= 0xFFFFFFFF
+    return rec
+
+
+def profile_power(rec: np.ndarray) -> np.ndarray:
+    """The error-vector power of a normalised record (combine_profile), as fx_value on the device."""
+    return rec[3].astype(np.float64) * B.FX_HI + rec[2].astype(np.float64) * B.FX_LO
 
 
 def shard(n: int, rank: int, world: int) -> tuple:
@@ -101,6 +155,13 @@ class LinkEngine:
         self.bps = self.plan.bits_per_ofdm_symbol
         self.adaptive = self.plan.adaptive
         self.cdtype = self.plan.cdtype
+        # bits per subcarrier (0 = inactive), for the per-subcarrier profile's rates
+        orders = np.array([int(len(l)).bit_length() - 1 for l in luts], dtype=np.int64)
+        if sc_lut is None:
+            self.bits_per_subcarrier = np.full(n_fft, orders[0], dtype=np.int64)
+        else:
+            sc = np.asarray(sc_lut, dtype=np.int64)
+            self.bits_per_subcarrier = np.where(sc >= 0, orders[np.maximum(sc, 0)], 0).astype(np.int64)
         self._lib = B.lib()
 
     # ------------------------------------------------------------------ helpers
@@ -137,11 +198,15 @@ class LinkEngine:
                                   B.ptr(y), B.ptr(stats)))
 
     def rx(self, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits_d, sym0, n_sym,
-           n_valid, counters, z_out=None, z_keep=0):
-        B.check(self._lib.ofdm_rx(self.plan.handle, stream, B.ptr(y), B.ptr(nr), B.ptr(ni), int(seed),
-                                  B.ptr(stats), int(total_samples), float(snr_db), int(noise_on), B.ptr(bits_d),
-                                  int(sym0), int(n_sym), int(n_valid), B.ptr(counters), B.ptr(z_out),
-                                  int(z_keep)))
+           n_valid, counters, z_out=None, z_keep=0, profile=None):
+        """ofdm_rx, or with a profile record (device int64 [5][N]) ofdm_rx_profile."""
+        args = (self.plan.handle, stream, B.ptr(y), B.ptr(nr), B.ptr(ni), int(seed), B.ptr(stats),
+                int(total_samples), float(snr_db), int(noise_on), B.ptr(bits_d), int(sym0), int(n_sym),
+                int(n_valid), B.ptr(counters), B.ptr(z_out), int(z_keep))
+        if profile is None:
+            B.check(self._lib.ofdm_rx(*args))
+        else:
+            B.check(self._lib.ofdm_rx_profile(*args, B.ptr(profile)))
 
     def reserve(self, n_sym: int, runs_in_flight: int = 2, group=None, lanes: int = 1) -> None:
         """Allocate, and hand back to torch's caching allocator, the channel-sample buffers of
@@ -174,7 +239,8 @@ class LinkEngine:
     def run_async(self, n_sym: int, snr_db: float, *, bits: Optional[np.ndarray] = None,
                   normals: Optional[tuple] = None, seed: int = 0, noise_on: bool = True, keep_symbols: int = 0,
                   group=None, y_budget: int = DEFAULT_Y_BUDGET, batch: Optional[int] = None,
-                  n_valid_bits: Optional[int] = None, events: Optional[list] = None) -> "PendingLink":
+                  n_valid_bits: Optional[int] = None, events: Optional[list] = None,
+                  profile: bool = False) -> "PendingLink":
         """Enqueue global OFDM symbols [0, n_sym) (this rank's shard when ``group`` is set) on
         the current stream without waiting for them; :meth:`PendingLink.result` reads the
         counts back.  Back-to-back calls therefore keep the GPU busy while the host prepares
@@ -185,6 +251,13 @@ class LinkEngine:
                   for Philox noise
         events  : if a list, (kernel, n_symbols, start, end) HIP events are appended around
                   every ofdm_tx / ofdm_rx launch (recorded on the launch stream)
+        profile : accumulate the per-subcarrier record of the whole run (LinkStats.profile): bit and
+                  symbol errors, error-vector power and clipped samples per subcarrier, summed on the
+                  device in integers by every batch and, with a group, over the ranks -- exact, so
+                  the same for any batching and rank count.  ofdm_rx_profile: the complex128 bench
+                  shapes with Philox streams and keep_symbols = 0 run their throughput receiver with
+                  the profile compiled in, every other run the generic receiver; run_pipelined takes
+                  no profile.
         """
         dev = self.device()
         stream = self.stream()
@@ -211,7 +284,11 @@ class LinkEngine:
             ni_d = self.upload(np.asarray(normals[1], np.float64))
 
         stats = new_stats(dev)
-        counters = torch.zeros(2, dtype=torch.int64, device=dev)
+        # the counters, and behind them the profile record: one buffer, one all-reduce
+        acc = torch.zeros(2 + (B.PROFILE_ROWS * N if profile else 0), dtype=torch.int64, device=dev)
+        counters = acc[:2]
+        prof = acc[2:].view(B.PROFILE_ROWS, N) if profile else None
+        pkw = {"profile": prof} if profile else {}  # (rx without a profile is called as before)
         csize = 8 if self.cdtype == torch.complex64 else 16
         per_batch = batch or max(1, min(mine, y_budget // (self.ystride * csize)))
         keep = min(keep_symbols, mine)
@@ -237,7 +314,7 @@ class LinkEngine:
             reduce_stats()
             self._timed(events, "ofdm_rx", mine, lambda: self.rx(
                 stream, y, nr_d, ni_d, seed, stats, samples, snr_db, noise_on, bits_d, lo, mine, n_valid,
-                counters, z_out, keep))
+                counters, z_out, keep, **pkw))
         else:
             # power pass first (the AWGN power is a whole-stream mean), then TX+RX per batch
             self.tx(stream, bits_d, seed, lo, mine, None, stats)
@@ -249,19 +326,20 @@ class LinkEngine:
                 self.tx(stream, bits_d, seed, b0, nb, y, scratch)
                 zk = keep if b0 == lo else 0
                 self.rx(stream, y, nr_d, ni_d, seed, stats, samples, snr_db, noise_on, bits_d, b0, nb,
-                        n_valid, counters, z_out if zk else None, zk)
+                        n_valid, counters, z_out if zk else None, zk, **pkw)
         work = None
         if group is not None:
             import torch.distributed as dist
 
             # off the critical path: the next run's TX does not wait for this reduction;
             # result() waits for it before reading the counters
-            work = dist.all_reduce(counters, op=dist.ReduceOp.SUM, group=group, async_op=True)
+            work = dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=group, async_op=True)
         done = None
         if dev.type == "cuda":
             done = torch.cuda.Event()
             done.record()  # on the launch stream: result() may be called under another stream
-        return PendingLink(n_sym, samples, stats, counters, z_out, done, work)
+        return PendingLink(n_sym, samples, stats, counters, z_out, done, work, prof,
+                           self.bits_per_subcarrier if profile else None)
 
 
     def lane_streams(self, lanes: int) -> list:
@@ -372,9 +450,11 @@ class LinkEngine:
 class PendingLink:
     """Device-side results of one :meth:`LinkEngine.run_async` call."""
 
-    def __init__(self, n_sym, samples, stats, counters, z_out, done=None, work=None):
+    def __init__(self, n_sym, samples, stats, counters, z_out, done=None, work=None, profile=None,
+                 bits_per_subcarrier=None):
         self.n_sym, self.samples = n_sym, samples
         self.stats, self.counters, self.z_out = stats, counters, z_out
+        self.profile, self.bits_per_subcarrier = profile, bits_per_subcarrier
         self.done = done
         self.work = work  # the asynchronous counter all-reduce (multi-rank), or None
 
@@ -392,8 +472,15 @@ class PendingLink:
         avg = st[1] / samples if samples else 0.0
         papr = float(10 * np.log10(st[2] / avg)) if avg > 0 else float("inf")
         z = self.z_out
+        prof = None
+        if self.profile is not None:
+            rec = combine_profile([self.profile.cpu().numpy()])
+            prof = SubcarrierProfile(bit_errors=rec[0], symbol_errors=rec[1], clipped=rec[4],
+                                     error_power=profile_power(rec), error_power_fx=rec[2:4].copy(),
+                                     n_symbols=self.n_sym,
+                                     bits_per_subcarrier=self.bits_per_subcarrier)
         return LinkStats(
             bit_errors=int(cnt[0]), symbol_errors=int(cnt[1]), num_ofdm_symbols=self.n_sym,
             power_sum=float(st[0]), x_power_sum=float(st[1]), x_peak=float(st[2]), samples=samples,
-            papr_db=papr, received=None if z is None else z.cpu().numpy().reshape(-1),
+            papr_db=papr, received=None if z is None else z.cpu().numpy().reshape(-1), profile=prof,
         )

@@ -136,7 +136,16 @@ class Simulation:
         received_symbols_keep: int = 64,
         make_plot: bool = True,
         process_group=None,
+        subcarrier_profile: bool = False,
     ):
+        """subcarrier_profile: also return the run's per-subcarrier results, accumulated on the GPU over
+        every OFDM symbol (engine.SubcarrierProfile): the keys ``bit_errors_per_subcarrier``,
+        ``symbol_errors_per_subcarrier``, ``error_power_per_subcarrier`` (sum of |z - c|^2 against the
+        transmitted point) and ``mer_db_per_subcarrier``.  Without it the result dict is unchanged.
+        Needs the fused path (the built-in modulators, prefixes and constellations).  A Simulation
+        taps ``received_symbols_keep`` = 64 symbols by default, so it takes the generic profile
+        kernel; ``received_symbols_keep=0`` with ``rng_mode='philox'`` reaches the throughput
+        receivers' profile kernels on the complex128 bench shapes."""
         if num_bits is None and num_symbols is None:
             raise ValueError("Either num_bits or num_symbols must be provided.")
         if num_bits is not None and num_symbols is not None:
@@ -168,6 +177,7 @@ class Simulation:
         self.received_symbols_keep = received_symbols_keep
         self.make_plot = make_plot
         self.process_group = process_group
+        self.subcarrier_profile = subcarrier_profile
 
     def _log(self, message: str) -> None:
         if self.verbose:
@@ -360,6 +370,8 @@ class Simulation:
                  and len(h_raw) - 1 <= N and cp <= N)
         if not fused and not reference:
             raise ValueError("rng_mode='philox' needs the built-in modulators, prefixes and constellations")
+        if not fused and self.subcarrier_profile:
+            raise ValueError("subcarrier_profile needs the built-in modulators, prefixes and constellations")
         t0 = time.perf_counter()
         if fused:
             luts, sc = (mapper.lut_tables() if adaptive else ([mapper.constellation], None))
@@ -375,11 +387,13 @@ class Simulation:
             seed = self.seed if self.seed is not None else 0
             st = engine.run(n_ofdm_syms, self.snr_db, bits=tx_bytes, normals=normals, seed=seed,
                             noise_on=noise_on, keep_symbols=self.received_symbols_keep,
-                            group=self.process_group, batch=self.batch_symbols, n_valid_bits=valid_bits)
+                            group=self.process_group, batch=self.batch_symbols, n_valid_bits=valid_bits,
+                            profile=self.subcarrier_profile)
             torch.cuda.synchronize()
             bit_errors, symbol_errors, papr_db = st.bit_errors, st.symbol_errors, st.papr_db
             received = st.received if st.received is not None else np.zeros(0, np.complex128)
             n_syms_total = n_ofdm_syms * N
+            profile = st.profile
         else:
             bit_errors, symbol_errors, papr_db, received, n_syms_total = self._composed_path(
                 tx_bytes, mapper, prefix_scheme, channel, sp, valid_bits)
@@ -396,6 +410,13 @@ class Simulation:
             "symbol_error_rate": ser,
             "received_symbols": received,
         })
+        if self.subcarrier_profile:
+            results.update({
+                "bit_errors_per_subcarrier": profile.bit_errors,
+                "symbol_errors_per_subcarrier": profile.symbol_errors,
+                "error_power_per_subcarrier": profile.error_power,
+                "mer_db_per_subcarrier": profile.mer_db,
+            })
         results["constellation_plot"] = self._plot(received, mapper, ber, papr_db, results["title"], orders)
         results["transmission_time_ms"] = elapsed * 1000
         results["bitrate_mbps"] = total_bits / 1e6  # the reference reports Mbit, not a rate (:807)
