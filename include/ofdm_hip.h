@@ -35,6 +35,10 @@ extern "C" {
 
 #define OFDM_ABI_VERSION 6
 
+/* SNR points one ofdm_rx_sweep call takes (the kernels hold a noise table per point in LDS and the
+ * points' SNRs in their arguments); a longer list is split into several calls over the same y. */
+#define OFDM_MAX_SWEEP_POINTS 40
+
 #define OFDM_OK 0
 #define OFDM_E_INVALID (-1)  /* bad argument / unsupported shape          */
 #define OFDM_E_HIP (-2)      /* HIP runtime error                          */
@@ -278,6 +282,34 @@ int ofdm_rx_profile(ofdm_plan_t plan, void* stream, const void* y, const double*
                     int32_t noise_on, const uint8_t* bits, int64_t sym0, int64_t n_sym,
                     int64_t n_valid_bits, uint64_t* counters, void* z_out, int64_t z_keep,
                     int64_t* profile);
+
+/*
+ * The one-pass SNR sweep receiver (an entry point added to ABI 6: nothing of the version's existing
+ * interface changes, so the number stands): ofdm_rx of the same channel samples at n_snr SNR points in
+ * one launch.  The transmitted stream, the tx bits and the noise words of throughput mode depend on
+ * (seed, symbol, N) only; the SNR enters through sigma and the MMSE noise variance.  So every symbol
+ * is read once, its lane block and noise words are drawn once, and per point the noise is scaled by
+ * the point's phase table and the symbol goes through ofdm_rx's FFT, equaliser, slicer and count:
+ * counters[2 k], counters[2 k + 1] += what ofdm_rx(..., snr_db[k], noise_on = 1, bits = NULL, ...)
+ * adds to its counters[0], counters[1] -- the same bits, noise words, sigma (from stats->power_sum /
+ * total_samples) and arithmetic per received sample; integer accumulation, so the counts do not
+ * depend on the grid, the batching, the rank count, the order of the points or how a list is split
+ * over calls.  The points share their noise realisation (common random numbers).
+ *
+ * Throughput streams only: no bits, nr / ni, z_out or profile; noise is always on.
+ * snr_db: HOST array [n_snr] -- the one host-side array of this ABI -- copied at the call (it may be
+ *   freed or changed once the call returns).
+ * counters: device uint64 [n_snr][2], accumulated.
+ * OFDM_E_INVALID, before any launch: n_snr outside [1, OFDM_MAX_SWEEP_POINTS], a non-finite SNR, a
+ *   plan with more than 8 bits on a subcarrier (as ofdm_rx with bits == NULL).  n_sym = 0: an empty call.
+ * Kernels (k_rx_sweep): the complex128 cyclic-prefix OFDM fixed-QAM bench shapes (64-QAM at N = 1024,
+ * 256-QAM at N = 4096) their throughput receiver's form, which keeps y and the noise radii in
+ * registers across the points; every other plan the generic receiver's, which reloads y and replays
+ * the lane generator per point.  A plan per point (adaptive loading re-derived per SNR) is not a sweep.
+ */
+int ofdm_rx_sweep(ofdm_plan_t plan, void* stream, const void* y, uint64_t seed, const ofdm_stats* stats,
+                  int64_t total_samples, const double* snr_db, int32_t n_snr, int64_t sym0, int64_t n_sym,
+                  int64_t n_valid_bits, uint64_t* counters);
 
 #ifdef __cplusplus
 }

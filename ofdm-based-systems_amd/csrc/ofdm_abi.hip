@@ -883,4 +883,40 @@ int ofdm_rx_profile(ofdm_plan_t p, void* stream, const void* y, const double* nr
                    n_sym, n_valid_bits, counters, z_out, z_keep, profile);
 }
 
+int ofdm_rx_sweep(ofdm_plan_t p, void* stream, const void* y, uint64_t seed, const ofdm_stats* stats,
+                  int64_t total_samples, const double* snr_db, int32_t n_snr, int64_t sym0, int64_t n_sym,
+                  int64_t n_valid_bits, uint64_t* counters) {
+    if (!p || !p->has_const) return fail(OFDM_E_INVALID, "ofdm_rx_sweep needs a constellation");
+    if (p->eq != OFDM_EQ_NONE && !p->has_channel) return fail(OFDM_E_INVALID, "plan has no channel response");
+    if (n_sym < 0 || sym0 < 0 || !counters) return fail(OFDM_E_INVALID, "bad argument to ofdm_rx_sweep");
+    if (n_snr < 1 || n_snr > OFDM_MAX_SWEEP_POINTS)
+        return fail(OFDM_E_INVALID, "ofdm_rx_sweep takes 1 to " + std::to_string(OFDM_MAX_SWEEP_POINTS) +
+                                        " SNR points per call, got " + std::to_string(n_snr));
+    if (!snr_db) return fail(OFDM_E_INVALID, "bad argument to ofdm_rx_sweep");
+    for (int k = 0; k < n_snr; ++k)
+        if (!std::isfinite(snr_db[k]))
+            return fail(OFDM_E_INVALID, "ofdm_rx_sweep: SNR point " + std::to_string(k) + " is not finite");
+    if (int rc = stream_bits_ok(p, nullptr, "ofdm_rx_sweep")) return rc;
+    if (n_sym == 0) return OFDM_OK;  // an empty call
+    if (!y || !stats || total_samples <= 0) return fail(OFDM_E_INVALID, "bad argument to ofdm_rx_sweep");
+    RxSweepArgs a{};
+    fill_common(p, a.r.c, nullptr, seed, sym0, n_sym, sym0 + n_sym);
+    a.r.y = y;
+    a.r.stats = (const double*)stats;
+    a.r.total_samples = total_samples;
+    a.r.noise_on = 1;
+    a.r.n_valid_bits = n_valid_bits;
+    a.r.counters = counters;
+    a.n_snr = n_snr;
+    for (int k = 0; k < n_snr; ++k) a.snr_lin[k] = std::pow(10.0, snr_db[k] / 10.0);  // (as ofdm_rx)
+    a.r.snr_lin = a.snr_lin[0];
+    int grid = 0;
+#define CALL(R) launch_rx_sweep<R>(p->logn, a, &grid, (hipStream_t)stream)
+    const hipError_t launch_result = DISPATCH(p, CALL);
+#undef CALL
+    if (launch_result == kLdsOverflow) return lds_overflow(p, "ofdm_rx_sweep");
+    HIPCHK(launch_result);
+    return OFDM_OK;
+}
+
 }  // extern "C"

@@ -1459,6 +1459,13 @@ __device__ __forceinline__ void build_noise_table(f32x2* ntab, double sigma, f64
     }
 }
 
+// Entry j of the table for sigma, as build_noise_table computes it (k_rx_sweep: a table per SNR point)
+__device__ __forceinline__ f32x2 noise_table_entry(double sigma, int j) {
+    const float s = (float)(sigma * kSqrt2Ln2);
+    const double th = (2.0 * j + 1.0) / kNoisePhases;
+    return f32x2{s * (float)cospi(th), s * (float)sinpi(th)};
+}
+
 // ------------------------------------------------------------------ constellation tables
 template <typename R>
 __device__ __forceinline__ int slice_axis(R u, const AxisInfo& a) {

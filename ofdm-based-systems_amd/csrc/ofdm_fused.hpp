@@ -1295,11 +1295,18 @@ struct RxLds {
     unsigned long long* redc;
     OP* ordt;
     uint8_t* wpat;  // wide plan: level -> index bits, [ipat | qpat] of kWideSide bytes per LUT
+    // k_rx_sweep: a noise phase table per SNR point (the complex128 throughput form: widened to
+    // double, as ntab64) and the workgroup's (bit errors, symbol errors) per point
+    f32x2* sntab;
+    f64x2* sntab64;
+    unsigned long long* scnt;
 };
 // n_wide (generic kernel): the LUTs of a plan with an order above 256 (side 32 / 64 slicer tables)
+// n_sweep (k_rx_sweep): the SNR points of the launch (<= OFDM_MAX_SWEEP_POINTS), 0 in every other kernel
+// (PROF: the one-wave-per-SIMD workgroup shape, which k_rx_sweep's throughput form takes too)
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool PROF = false, typename CV>
 __host__ __device__ __forceinline__ constexpr RxLds<R> rx_carve(CV& cv, int words_per_sym, int tts_all,
-                                                                int n_wide = 0) {
+                                                                int n_wide = 0, int n_sweep = 0) {
     constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV, PROF>();
     using G = Geo<LOGN, BLK>;
     using C = cpx<R>;
@@ -1319,6 +1326,10 @@ __host__ __device__ __forceinline__ constexpr RxLds<R> rx_carve(CV& cv, int word
     // global table, every element paid an L2 round trip with a vmcnt(0) per symbol
     m.eqt = cv.template take<C>(eq_in_lds<R, FB, LOGN, EQ>() ? G::N : 0);
     m.wpat = cv.template take<uint8_t>(FB == 0 ? (size_t)n_wide * 2 * kWideSide : 0);
+    constexpr bool F64_FAST = sizeof(R) == 8 && FB > 0;
+    m.sntab = cv.template take<f32x2>(F64_FAST ? 0 : (size_t)n_sweep * kNoisePhases);
+    m.sntab64 = cv.template take<f64x2>(F64_FAST ? (size_t)n_sweep * kNoisePhases : 0);
+    m.scnt = cv.template take<unsigned long long>((size_t)n_sweep * 2);
     return m;
 }
 
@@ -1363,7 +1374,7 @@ __device__ __forceinline__ void prof_power(cpx<R> z, cpx<R> c, unsigned long lon
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
 __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB, LOGN, EQ, MV>())) void k_rx(
     RxArgs a) {
-    constexpr bool PROF = false;
+    constexpr bool PROF = false, SWEEP = false;
 #include "ofdm_rx_body.hpp"
 }
 
@@ -1373,8 +1384,26 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB,
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
 __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<R, FB, LOGN, EQ, MV, true>())) void k_rx_prof(
     RxArgs a) {
-    constexpr bool PROF = true;
+    constexpr bool PROF = true, SWEEP = false;
 #include "ofdm_rx_body.hpp"
+}
+
+// The one-pass SNR sweep receiver (ofdm_rx_sweep): every symbol is received once per SNR point of the
+// launch -- y read, the lane block and the noise words drawn once per symbol; per point the noise
+// scaled by the point's phase table, then the FFT, MMSE variance, equaliser, slicer and count of k_rx
+// (the same body), so that point k's counts are those of a k_rx launch at snr_db[k].  Throughput
+// streams only.  Instantiated for the generic kernel (FB = 0: every plan that runs Philox streams) and
+// for the complex128 cyclic-prefix OFDM fixed-QAM bench shapes (ofdm_sweep_inst.hpp); the throughput
+// form keeps y (64 VGPRs), the radii and the phase words in registers across the points, so it takes
+// the profile's one-wave-per-SIMD workgroup shape (rx_block / rx_waves with PROF).
+template <typename R, int LOGN, int EQ, int FB, bool MV>
+__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<R, FB, LOGN, EQ, MV, true>())) void k_rx_sweep(
+    RxSweepArgs sa) {
+    constexpr bool PROF = false, SWEEP = true, REF = false, WIDE = false;
+    const RxArgs& a = sa.r;  // (a copy of its own that took each point's snr_lin in turn left the argument registers for memory)
+#define OFDM_RX_BODY_SWEEP
+#include "ofdm_rx_body.hpp"
+#undef OFDM_RX_BODY_SWEEP
 }
 
 }  // namespace ofdm

@@ -185,6 +185,14 @@ struct RxArgs {
     int64_t* profile;
 };
 
+// ofdm_rx_sweep: the receiver's arguments (counters: device uint64[n_snr][2]; snr_lin, noise_on,
+// nr / ni, z_out, wide and profile of `r` unused: noise is always on) and the points' 10^(snr_db/10)
+struct RxSweepArgs {
+    RxArgs r;
+    int n_snr;
+    double snr_lin[OFDM_MAX_SWEEP_POINTS];
+};
+
 // complex elements per symbol row of the fused TX: the FFT's padded row, or the extended stream if longer
 constexpr int tx_slot(int logn, int cp, int L) {
     const int ext = (1 << logn) + cp + (L > 1 ? L - 1 : 0);
@@ -229,6 +237,10 @@ hipError_t launch_rx(int logn, const RxArgs& a, int* grid, hipStream_t s);
 // the receiver with the per-subcarrier profile (a.profile set; ofdm_prof_inst.hpp)
 template <typename R>
 hipError_t launch_rx_prof(int logn, const RxArgs& a, int* grid, hipStream_t s);
+
+// the one-pass SNR sweep receiver (ofdm_sweep_inst.hpp)
+template <typename R>
+hipError_t launch_rx_sweep(int logn, const RxSweepArgs& a, int* grid, hipStream_t s);
 
 hipError_t launch_finalize(const double* partials, int nblocks, int nfields, int max_mask,
                            double* stats, hipStream_t s);

@@ -1,11 +1,21 @@
 // ofdm_rx_body.hpp -- the body of the fused receivers k_rx and k_rx_prof (ofdm_fused.hpp), included
 // into each kernel after its `constexpr bool PROF` (no include guard: included once per kernel).
 // In scope: the kernel's template parameters R, LOGN, EQ, FB, MV, REF, WIDE, its argument `RxArgs a`,
-// and PROF.
+// PROF and SWEEP.
+// SWEEP (k_rx_sweep only, which defines OFDM_RX_BODY_SWEEP around its include and has its argument
+// `RxSweepArgs sa` in scope, `a` being sa.r): every symbol is received once per SNR
+// point, the point loop opened and closed under that macro so that the other kernels' text has no loop.
     static_assert(!WIDE || (FB == 0 && EQ == -1 && !REF), "the wide slicer lives in the generic kernel");
     static_assert(!PROF || (!REF && (FB == 0 || (sizeof(R) == 8 && (FB == 1 || !(FB & 1)) && (FB == 1 || !MV)))),
                   "the profile: the generic kernel, or a complex128 cyclic-prefix OFDM QAM throughput receiver");
-    constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV, PROF>();
+    static_assert(!SWEEP || (!REF && !WIDE && !PROF && (FB == 0 || (sizeof(R) == 8 && FB > 1 && !(FB & 1) && !MV))),
+                  "the sweep: the generic kernel, or a complex128 cyclic-prefix OFDM fixed-QAM throughput receiver");
+#ifdef OFDM_RX_BODY_SWEEP
+#define OFDM_RX_SNR_LIN snr_lin_pt  // the SNR of the point being received
+#else
+#define OFDM_RX_SNR_LIN a.snr_lin
+#endif
+    constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV, PROF || SWEEP>();
     using G = Geo<LOGN, BLK>;
     using C = cpx<R>;
     constexpr int N = G::N, E = G::E, TPS = G::TPS;
@@ -36,7 +46,15 @@
     const int tts_all = rx_tts<R, LOGN, FB>(scm);
     // a plan with an order above 256 (WIDE): the wide slicer's level patterns in LDS
     const int n_wide = WIDE ? cm.n_axis : 0;
-    const RxLds<R> lds = rx_carve<R, LOGN, EQ, FB, MV, PROF>(cv, cm.words_per_sym, tts_all, n_wide);
+    // SWEEP: the per-point noise tables and counters (the throughput form keeps y and the noise radii
+    // in registers across the points, HOLD; the generic one reloads y and replays the generator)
+#ifdef OFDM_RX_BODY_SWEEP
+    const int n_sweep = sa.n_snr;
+#else
+    constexpr int n_sweep = 0;
+#endif
+    constexpr bool HOLD = SWEEP && F64_FAST;
+    const RxLds<R> lds = rx_carve<R, LOGN, EQ, FB, MV, PROF || SWEEP>(cv, cm.words_per_sym, tts_all, n_wide, n_sweep);
     C *tw = lds.tw, *tt = lds.tt, *eqt = lds.eqt;
     AxisInfo* axis = lds.axis;
     unsigned char* rowmem = lds.rowmem;
@@ -72,6 +90,21 @@
     }
     const R sigma = (R)sigma_d;
     build_noise_table(ntab, sigma_d, ntab64);
+#ifdef OFDM_RX_BODY_SWEEP
+    // one phase table per point, each entry as build_noise_table makes it from the point's sigma (the
+    // single table above is not read), and the workgroup's per-point counts zeroed
+    {
+        const double pw = a.stats[0] / (double)a.total_samples;
+        for (int i = threadIdx.x; i < n_sweep * kNoisePhases; i += BLK) {
+            const f32x2 e = noise_table_entry(sqrt((pw / sa.snr_lin[i / kNoisePhases]) / 2.0), i % kNoisePhases);
+            if constexpr (HOLD)
+                lds.sntab64[i] = f64x2{(double)e.x, (double)e.y};
+            else
+                lds.sntab[i] = e;
+        }
+        for (int i = threadIdx.x; i < 2 * n_sweep; i += BLK) lds.scnt[i] = 0;
+    }
+#endif
     if constexpr (!TT) load_twiddles<R>(tw, (const C*)cm.tw);
     st_tt.store(tt);
     if constexpr (EQ_LDS) st_eq.store(eqt);
@@ -225,7 +258,47 @@
         const C* ys = (const C*)a.y + sl * ystride;
         C x[E];
         tb.load(cm, sg, t, W, active && (!(flags & 4) || (noise && !array_noise)));
-        load_sym(sl, x);
+#ifdef OFDM_RX_BODY_SWEEP
+        // What does not depend on the SNR, once per symbol: the lane block (above) and, HOLD, the kept
+        // samples and the lane's noise words -- the 16 float32 radii and the four phase words stay in
+        // registers across the points.  The generic form keeps the generator's state instead and, per
+        // point, reloads y (cached) and draws the same words again: zero padding's tail samples too.
+        [[maybe_unused]] C y0[HOLD ? E : 1];
+        [[maybe_unused]] float rad[HOLD ? E : 1] = {};
+        [[maybe_unused]] uint32_t qw[HOLD ? E / 4 : 1] = {};
+        const uint32_t g0x = tb.g.x, g0c = tb.g.c;
+        if constexpr (HOLD) {
+            load_sym(sl, y0);
+            if (active && noise) {
+#pragma unroll
+                for (int i = 0; i < E; ++i) {
+                    const uint32_t w = tb.g.draw(i);
+                    if ((i & 3) == 0) qw[i >> 2] = tb.g.q;
+                    rad[i] = noise_radius(w);
+                }
+            }
+        }
+        for (int pt = 0; pt < n_sweep; ++pt) {
+        const double snr_lin_pt = sa.snr_lin[pt];  // (the MMSE noise variance's: OFDM_RX_SNR_LIN)
+        // the point's phase table under the single-point table's name: the noise code below is k_rx's
+        [[maybe_unused]] const f32x2* const ntab = lds.sntab + pt * kNoisePhases;
+        if constexpr (HOLD) {
+            // x = y + noise_k as add_noise64 forms it, from the held radius and phase words
+            const f64x2* const tab64 = lds.sntab64 + pt * kNoisePhases;
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                const uint32_t off = ((qw[i >> 2] >> (8 * (i & 3))) & (uint32_t)(kNoisePhases - 1)) * (uint32_t)sizeof(f64x2);
+                const f64x2 e = *(const f64x2*)((const unsigned char*)tab64 + off);
+                const double rd = (double)rad[i];
+                x[i].re = __builtin_fma(rd, e.x, y0[i].re);
+                x[i].im = __builtin_fma(rd, e.y, y0[i].im);
+            }
+        } else {
+            tb.g.x = g0x;
+            tb.g.c = g0c;
+        }
+#endif
+        if constexpr (!HOLD) load_sym(sl, x);
         if (active && array_noise) {
             const double* nr = a.nr + sg * (N + cp) + (zp ? 0 : cp);
             const double* ni = a.ni + sg * (N + cp) + (zp ? 0 : cp);
@@ -234,7 +307,7 @@
                 x[i].re += sigma * (R)nr[t + i * TPS];
                 x[i].im += sigma * (R)ni[t + i * TPS];
             }
-        } else if (active && noise) {
+        } else if (active && noise && !HOLD) {
             // noise sample j = i of the lane: a radius word per element, a phase word per four
             // (stream version 3, ofdm_device.hpp "throughput-mode streams")
 #pragma unroll
@@ -312,7 +385,7 @@
             }
             p = group_sum<R, TPS>(p, red);
             if constexpr (FB > 0) p *= scale * scale;  // power of the ortho-scaled spectrum
-            nv = cm.gain_mean == 0.0 ? (R)INFINITY : ((p / (R)N) / (R)a.snr_lin) / (R)cm.gain_mean;
+            nv = cm.gain_mean == 0.0 ? (R)INFINITY : ((p / (R)N) / (R)OFDM_RX_SNR_LIN) / (R)cm.gain_mean;
         }
         if (scm) {
             // single carrier: equalise every subcarrier, back to time with ifft(ortho)
@@ -545,7 +618,24 @@
             be += bes;
             se += ses;
         }
+#ifdef OFDM_RX_BODY_SWEEP
+        // this symbol's counts at this point (a lane's: <= 128 bit and 16 symbol errors, so both fit one
+        // word through the wave's sum) into the workgroup's pair of the point
+        {
+            unsigned long long v = be | (se << 32);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+            if ((threadIdx.x & 63) == 0 && v) {
+                atomicAdd(&lds.scnt[2 * pt], v & 0xFFFFFFFFull);
+                atomicAdd(&lds.scnt[2 * pt + 1], v >> 32);
+            }
+            be = se = 0;
+        }
+#endif
         sym_sync<TPS>();  // W and the FFT row are rewritten by the next symbol
+#ifdef OFDM_RX_BODY_SWEEP
+        }  // (the point loop: the next point's FFT rewrites the row too)
+#endif
     }
     be = block_sum<unsigned long long, BLK>(be, redc);
     se = block_sum<unsigned long long, BLK>(se, redc);
@@ -553,6 +643,14 @@
         if (be) atomicAdd((unsigned long long*)&a.counters[0], be);
         if (se) atomicAdd((unsigned long long*)&a.counters[1], se);
     }
+#ifdef OFDM_RX_BODY_SWEEP
+    // (be and se are zero here, and block_sum's barriers stand between the points' LDS sums and this
+    // read)  counters[n_snr][2]: one integer atomic pair per point and workgroup
+    for (int i = threadIdx.x; i < 2 * n_sweep; i += BLK) {
+        const unsigned long long v = lds.scnt[i];
+        if (v) atomicAdd((unsigned long long*)&a.counters[i], v);
+    }
+#endif
     if constexpr (PROF) {
         // row by row: every lane writes its elements into its symbol slot (SPB x N 64-bit words
         // over the FFT rows, which hold at least 8 bytes per element), the slots are summed per
@@ -584,3 +682,4 @@
             }
         });
     }
+#undef OFDM_RX_SNR_LIN

@@ -27,7 +27,10 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib",
 # ABI 5: throughput-mode stream version 3 (the noise radius takes the whole lane word, the phase
 # its own word per four samples; csrc/ofdm_device.hpp "throughput-mode streams")
 # ABI 6: ofdm_rx_profile (the fused receiver with a per-subcarrier error / EVM record)
+# (ofdm_rx_sweep, the one-pass SNR sweep receiver, joined ABI 6 as an added entry point)
 ABI_VERSION = 6
+# SNR points one ofdm_rx_sweep call takes (OFDM_MAX_SWEEP_POINTS, include/ofdm_hip.h)
+MAX_SWEEP_POINTS = 40
 
 OFDM_F32, OFDM_F64 = 0, 1
 # ofdm_stats (include/ofdm_hip.h): power_sum, x_power_sum, x_peak (double), power_fx[2] (int64)
@@ -110,6 +113,8 @@ SIGNATURES = {
                                _I64, _VP, _VP, _I64]),
     "ofdm_rx_profile": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _I64, _F64, _I32, _VP, _I64, _I64,
                                        _I64, _VP, _VP, _I64, _VP]),
+    # (snr_db: a host array of doubles, copied at the call)
+    "ofdm_rx_sweep": (ctypes.c_int, [_VP, _VP, _VP, _U64, _VP, _I64, _c_f64p, _I32, _I64, _I64, _I64, _VP]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

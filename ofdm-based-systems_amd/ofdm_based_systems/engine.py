@@ -24,10 +24,14 @@ all-gather of the 40-byte ofdm_stats record per rank (the AWGN power is a whole-
 mean, noise/models.py:14, kept as an exact fixed-point sum so that sigma does not depend
 on the rank count) and one all-reduce of the two u64 counters -- with ``profile=True`` of the
 counters and the per-subcarrier record behind them (integers: the sum is exact).
+
+SNR sweeps: :meth:`LinkEngine.run_sweep` transmits once and receives at every SNR of a list in one
+pass (ofdm_rx_sweep); point k is ``run(n_sym, snr_k, seed=seed)``.
 """
 
 from __future__ import annotations
 
+import ctypes
 import math
 from dataclasses import dataclass, field
 from typing import Optional, Sequence
@@ -208,6 +212,14 @@ class LinkEngine:
         else:
             B.check(self._lib.ofdm_rx_profile(*args, B.ptr(profile)))
 
+    def rx_sweep(self, stream, y, seed, stats, total_samples, snr_dbs, sym0, n_sym, n_valid, counters):
+        """ofdm_rx_sweep: the receiver at every SNR of ``snr_dbs`` (at most B.MAX_SWEEP_POINTS, a host
+        list copied at the call) over the same y; counters: device int64 [len(snr_dbs)][2], accumulated."""
+        snrs = (ctypes.c_double * len(snr_dbs))(*[float(q) for q in snr_dbs])
+        B.check(self._lib.ofdm_rx_sweep(self.plan.handle, stream, B.ptr(y), int(seed), B.ptr(stats),
+                                        int(total_samples), snrs, len(snr_dbs), int(sym0), int(n_sym),
+                                        int(n_valid), B.ptr(counters)))
+
     def reserve(self, n_sym: int, runs_in_flight: int = 2, group=None, lanes: int = 1) -> None:
         """Allocate, and hand back to torch's caching allocator, the channel-sample buffers of
         ``runs_in_flight`` concurrent runs of n_sym global symbols (run_pipelined keeps two
@@ -341,6 +353,92 @@ class LinkEngine:
         return PendingLink(n_sym, samples, stats, counters, z_out, done, work, prof,
                            self.bits_per_subcarrier if profile else None)
 
+
+    # ------------------------------------------------------------------ one-pass SNR sweep
+    def run_sweep(self, n_sym: int, snr_dbs, **kw) -> list:
+        """A BER curve from one transmit: the counts of :meth:`run` at every SNR of ``snr_dbs`` (see
+        :meth:`run_sweep_async`), one LinkStats per point in the order given."""
+        return self.run_sweep_async(n_sym, snr_dbs, **kw).result()
+
+    def run_sweep_async(self, n_sym: int, snr_dbs, *, seed: int = 0, group=None,
+                        y_budget: int = DEFAULT_Y_BUDGET, batch: Optional[int] = None,
+                        n_valid_bits: Optional[int] = None, events: Optional[list] = None) -> "PendingSweep":
+        """Throughput-mode (Philox) runs of global OFDM symbols [0, n_sym) at every SNR of
+        ``snr_dbs`` with one seed, from one transmit: point k is ``run(n_sym, snr_dbs[k], seed=seed)``
+        -- the same bits, noise words, sigma and per-sample arithmetic, so in complex128 the same
+        counts -- but the stream is transmitted, written and read once per batch, and the receiver
+        (``ofdm_rx_sweep``) draws each symbol's noise words once for all points.  The points share
+        their noise realisation (common random numbers: a smooth, monotone curve).
+
+        The schedule is :meth:`run_async`'s: the whole shard resident, or a power pass and then
+        TX + sweep-RX per batch; one statistics all-gather per run and one asynchronous all-reduce
+        of the [K][2] counters.  A list longer than B.MAX_SWEEP_POINTS is split into several
+        receiver launches over the same y.  The counts do not depend on the batching, the rank
+        count, the order of the list or how it is split.
+
+        Not taken: caller bits or normals, orders above 256, a profile, a received-symbol tap, and
+        a plan per point (adaptive loading re-derived per SNR)."""
+        snrs = [float(q) for q in snr_dbs]
+        if not snrs:
+            raise ValueError("run_sweep needs at least one SNR point")
+        if not all(math.isfinite(q) for q in snrs):
+            raise ValueError("run_sweep needs finite SNR points")
+        K = len(snrs)
+        dev = self.device()
+        stream = self.stream()
+        world, rank = 1, 0
+        if group is not None:
+            import torch.distributed as dist
+
+            world, rank = dist.get_world_size(group), dist.get_rank(group)
+        lo, hi = shard(n_sym, rank, world)
+        mine = hi - lo
+        N, cp = self.n_fft, self.cp
+        samples = n_sym * (N + cp)
+        n_valid = self.valid_bits(n_sym) if n_valid_bits is None else int(n_valid_bits)
+        stats = new_stats(dev)
+        counters = torch.zeros((K, 2), dtype=torch.int64, device=dev)
+        csize = 8 if self.cdtype == torch.complex64 else 16
+        per_batch = batch or max(1, min(mine, y_budget // (self.ystride * csize)))
+
+        def reduce_stats():  # (as run_async)
+            if group is not None:
+                import torch.distributed as dist
+
+                parts = [torch.empty_like(stats) for _ in range(world)]
+                dist.all_gather(parts, stats, group=group)
+                combine_stats(stats, parts)
+
+        def sweep(y, sym0, n):
+            for k0 in range(0, K, B.MAX_SWEEP_POINTS):
+                k1 = min(K, k0 + B.MAX_SWEEP_POINTS)
+                self._timed(events, "ofdm_rx_sweep", n, lambda: self.rx_sweep(
+                    stream, y, seed, stats, samples, snrs[k0:k1], sym0, n, n_valid, counters[k0:k1]))
+
+        if per_batch >= mine:
+            y = torch.empty((max(mine, 1), self.ystride), dtype=self.cdtype, device=dev)
+            self._timed(events, "ofdm_tx", mine, lambda: self.tx(stream, None, seed, lo, mine, y, stats))
+            reduce_stats()
+            sweep(y, lo, mine)
+        else:
+            self.tx(stream, None, seed, lo, mine, None, stats)
+            reduce_stats()
+            scratch = new_stats(dev)
+            y = torch.empty((per_batch, self.ystride), dtype=self.cdtype, device=dev)
+            for b0 in range(lo, hi, per_batch):
+                nb = min(per_batch, hi - b0)
+                self.tx(stream, None, seed, b0, nb, y, scratch)
+                sweep(y, b0, nb)
+        work = None
+        if group is not None:
+            import torch.distributed as dist
+
+            work = dist.all_reduce(counters, op=dist.ReduceOp.SUM, group=group, async_op=True)
+        done = None
+        if dev.type == "cuda":
+            done = torch.cuda.Event()
+            done.record()
+        return PendingSweep(n_sym, samples, stats, counters, done, work)
 
     def lane_streams(self, lanes: int) -> list:
         """The current stream and lanes - 1 more, kept per engine (their allocator pools persist:
@@ -484,3 +582,25 @@ class PendingLink:
             power_sum=float(st[0]), x_power_sum=float(st[1]), x_peak=float(st[2]), samples=samples,
             papr_db=papr, received=None if z is None else z.cpu().numpy().reshape(-1), profile=prof,
         )
+
+
+class PendingSweep:
+    """Device-side results of one :meth:`LinkEngine.run_sweep_async` call: the [K][2] counters and
+    the run's one statistics record."""
+
+    def __init__(self, n_sym, samples, stats, counters, done=None, work=None):
+        self.n_sym, self.samples = n_sym, samples
+        self.stats, self.counters = stats, counters
+        self.done, self.work = done, work
+
+    def result(self) -> list:
+        """One LinkStats per SNR point, in the order given: the point's counts and the run's shared
+        power / PAPR fields."""
+        # (PendingLink waits for the launch stream and the counter all-reduce and packages the statistics)
+        shared = PendingLink(self.n_sym, self.samples, self.stats, self.counters[0], None, self.done,
+                             self.work).result()
+        self.done = self.work = None
+        cnt = self.counters.cpu().numpy()
+        return [LinkStats(bit_errors=int(c[0]), symbol_errors=int(c[1]), num_ofdm_symbols=self.n_sym,
+                          power_sum=shared.power_sum, x_power_sum=shared.x_power_sum, x_peak=shared.x_peak,
+                          samples=shared.samples, papr_db=shared.papr_db) for c in cnt]

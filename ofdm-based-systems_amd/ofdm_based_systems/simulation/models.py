@@ -258,6 +258,65 @@ class Simulation:
 
     # ------------------------------------------------------------------ run
     def run(self) -> Dict[str, Any]:
+        return self._run()
+
+    @classmethod
+    def run_sweep(cls, simulations: List["Simulation"]) -> List[Dict[str, Any]]:
+        """The results of ``[s.run() for s in simulations]`` for the simulations of one SNR sweep
+        (the list create_from_simulation_settings returns) from ONE engine sweep
+        (LinkEngine.run_sweep): the stream is transmitted once and received at every SNR, where
+        running them one by one transmits it again per point.  One result dict per simulation, with
+        the keys and values ``run()`` gives (``transmission_time_ms`` is the whole sweep's).
+
+        Raises ValueError unless the simulations differ only in ``snr_db``, use
+        ``rng_mode='philox'``, are FIXED mode with the built-in strategies and AWGN, and have
+        ``received_symbols_keep == 0`` and no ``subcarrier_profile`` (the sweep receiver has no
+        caller streams, no plan per point, no received-symbol tap and no profile)."""
+        sims = list(simulations)
+        if not sims:
+            return []
+
+        def same(a, b):
+            if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+                return a is not None and b is not None and np.array_equal(a, b)
+            return a is b or a == b
+
+        first = vars(sims[0])
+        for s in sims[1:]:
+            for key, val in vars(s).items():
+                if key != "snr_db" and not same(val, first[key]):
+                    raise ValueError(f"run_sweep: the simulations differ in more than snr_db ({key})")
+        s0 = sims[0]
+        if s0.rng_mode != "philox":
+            raise ValueError("run_sweep needs rng_mode='philox' (the sweep receiver generates its streams)")
+        builtin = (cls.MODULATOR_SCHEME_MAPPERS.get(s0.modulator_type) in (OFDMModulator, SingleCarrierOFDMModulator)
+                   and cls.PREFIX_SCHEME_MAPPERS.get(s0.prefix_scheme) in (
+                       CyclicPrefixScheme, ZeroPaddingPrefixScheme, NoPrefixScheme)
+                   and cls.CONSTELLATION_SCHEME_MAPPERS.get(s0.constellation_scheme) in (
+                       QAMConstellationMapper, PSKConstellationMapper)
+                   and cls.NOISE_SCHEME_MAPPERS.get(s0.noise_scheme, AWGNoiseModel) is AWGNoiseModel)
+        if s0.adaptive_modulation_mode != AdaptiveModulationMode.FIXED or not builtin:
+            raise ValueError("run_sweep needs FIXED mode with the built-in modulators, prefixes, constellations "
+                             "and AWGN (adaptive loading is a different plan per SNR)")
+        if s0.received_symbols_keep != 0 or s0.subcarrier_profile:
+            raise ValueError("run_sweep needs received_symbols_keep=0 and no subcarrier_profile")
+
+        swept: List[Any] = []  # the engine sweep's LinkStats, filled by the first simulation
+
+        def link(k):
+            def stats(make_engine, n_sym, seed, valid_bits):
+                if not swept:
+                    swept.extend(make_engine().run_sweep(
+                        n_sym, [s.snr_db for s in sims], seed=seed, group=s0.process_group,
+                        batch=s0.batch_symbols, n_valid_bits=valid_bits))
+                return swept[k]
+            return stats
+
+        return [s._run(link(k)) for k, s in enumerate(sims)]
+
+    def _run(self, link=None) -> Dict[str, Any]:
+        """run(); ``link`` (run_sweep): a callable (make_engine, n_sym, seed, valid_bits) -> LinkStats
+        standing in for this simulation's own engine run."""
         results: Dict[str, Any] = {}
         sp = SerialToParallelConverter()
         noise_model = self.NOISE_SCHEME_MAPPERS.get(self.noise_scheme, AWGNoiseModel)()
@@ -372,23 +431,30 @@ class Simulation:
             raise ValueError("rng_mode='philox' needs the built-in modulators, prefixes and constellations")
         if not fused and self.subcarrier_profile:
             raise ValueError("subcarrier_profile needs the built-in modulators, prefixes and constellations")
+        if not fused and link is not None:
+            raise ValueError("run_sweep needs the fused path (channel order and prefix within n_fft)")
         t0 = time.perf_counter()
         if fused:
             luts, sc = (mapper.lut_tables() if adaptive else ([mapper.constellation], None))
             prec = B.OFDM_F32 if self.precision == "f32" else B.OFDM_F64
-            engine = LinkEngine(N, cp, h_raw, _EQ_KIND[self.equalizator_type], luts, sc, prec,
-                                prefix=B.PREFIX_ZERO if pre_cls is ZeroPaddingPrefixScheme else B.PREFIX_CYCLIC,
-                                modulator=B.MOD_SC if mod_cls is SingleCarrierOFDMModulator else B.MOD_OFDM)
+            def make_engine():
+                return LinkEngine(N, cp, h_raw, _EQ_KIND[self.equalizator_type], luts, sc, prec,
+                                  prefix=B.PREFIX_ZERO if pre_cls is ZeroPaddingPrefixScheme else B.PREFIX_CYCLIC,
+                                  modulator=B.MOD_SC if mod_cls is SingleCarrierOFDMModulator else B.MOD_OFDM)
+
             noise_on = isinstance(noise_model, AWGNoiseModel)
             normals = None
             if reference and noise_on:
                 n_samp = n_ofdm_syms * (N + cp)
                 normals = (np.random.normal(size=n_samp), np.random.normal(size=n_samp))
             seed = self.seed if self.seed is not None else 0
-            st = engine.run(n_ofdm_syms, self.snr_db, bits=tx_bytes, normals=normals, seed=seed,
-                            noise_on=noise_on, keep_symbols=self.received_symbols_keep,
-                            group=self.process_group, batch=self.batch_symbols, n_valid_bits=valid_bits,
-                            profile=self.subcarrier_profile)
+            if link is not None:
+                st = link(make_engine, n_ofdm_syms, seed, valid_bits)
+            else:
+                st = make_engine().run(n_ofdm_syms, self.snr_db, bits=tx_bytes, normals=normals, seed=seed,
+                                       noise_on=noise_on, keep_symbols=self.received_symbols_keep,
+                                       group=self.process_group, batch=self.batch_symbols,
+                                       n_valid_bits=valid_bits, profile=self.subcarrier_profile)
             torch.cuda.synchronize()
             bit_errors, symbol_errors, papr_db = st.bit_errors, st.symbol_errors, st.papr_db
             received = st.received if st.received is not None else np.zeros(0, np.complex128)

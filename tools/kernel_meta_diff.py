@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Per-kernel metadata of two builds of libofdm_hip.so, side by side (the comparison DESIGN.md
+section 6 describes): vgpr_count, vgpr_spill_count, sgpr_spill_count and group_segment_fixed_size of
+every kernel, from `llvm-readelf --notes` on the library's gfx950 code objects.
+
+    tools/kernel_meta_diff.py PARENT.so THIS.so > profiles/<name>_kernel_audit.txt
+
+Kernels of PARENT.so are compared by name; kernels only in THIS.so are listed with their figures.
+Needs no GPU.  Exit status 1 if a kernel of the parent build differs or is missing.
+"""
+import argparse
+import os
+import re
+import struct
+import subprocess
+import sys
+import tempfile
+
+MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+FIELDS = ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "group_segment_fixed_size")
+LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/llvm/bin")
+
+
+def code_objects(path, arch="gfx950"):
+    """The device code objects for `arch` of every offload bundle in the file."""
+    data = open(path, "rb").read()
+    pos = data.find(MAGIC)
+    while pos >= 0:
+        (count,) = struct.unpack_from("<Q", data, pos + len(MAGIC))
+        q = pos + len(MAGIC) + 8
+        for _ in range(count):
+            off, size, tlen = struct.unpack_from("<QQQ", data, q)
+            triple = data[q + 24:q + 24 + tlen].decode()
+            q += 24 + tlen
+            if arch in triple and size:
+                yield data[pos + off:pos + off + size]
+        pos = data.find(MAGIC, pos + 1)
+
+
+def kernels(path):
+    """{demangled kernel name: (the four FIELDS)} of a library."""
+    out = {}
+    for co in code_objects(path):
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(co)
+            f.flush()
+            notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", f.name], check=True,
+                                   capture_output=True, text=True).stdout
+        for block in re.split(r"\n  - ", notes):
+            name = re.search(r"\.name:\s+(\S+)", block)
+            vals = [re.search(r"\.%s:\s+(\d+)" % k, block) for k in FIELDS]
+            if name and all(vals):
+                out[name.group(1).strip("'\"")] = tuple(int(v.group(1)) for v in vals)
+    names = list(out)
+    dem = subprocess.run(["c++filt"], input="\n".join(names), check=True,
+                         capture_output=True, text=True).stdout.split("\n")
+    return {re.sub(r"^void ofdm::|\(.*\)$", "", d): out[n] for n, d in zip(names, dem)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("parent")
+    ap.add_argument("this")
+    a = ap.parse_args()
+    old, new = kernels(a.parent), kernels(a.this)
+    fused = [k for k in old if k.startswith(("k_tx<", "k_rx<", "k_rx_prof<"))]
+    other = [k for k in old if k not in fused]
+    diff_f = [k for k in fused if new.get(k) != old[k]]
+    diff_o = [k for k in other if new.get(k) != old[k]]
+    print("# Kernel metadata of libofdm_hip.so (llvm-readelf --notes on its gfx950 code objects), parent commit "
+          "against this\n# commit: " + ", ".join(FIELDS) + " per kernel.")
+    n = lambda p: sum(k.startswith(p) for k in fused)
+    print(f"# fused kernels of the parent build: {len(fused)} (k_tx {n('k_tx<')}, k_rx {n('k_rx<')}, k_rx_prof "
+          f"{n('k_rx_prof<')}); with different figures in this build: {len(diff_f)}")
+    print(f"# other kernels of the parent build: {len(other)}, different: {len(diff_o)}")
+    for k in diff_f + diff_o:
+        print("# DIFFERENT:", k, old[k], "->", new.get(k))
+    print("# new kernels: name  " + "  ".join(FIELDS))
+    for k in sorted(set(new) - set(old)):
+        print(k, *new[k])
+    return 1 if diff_f or diff_o else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
