@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -827,30 +828,48 @@ int ofdm_tx(ofdm_plan_t p, void* stream, const uint8_t* bits, uint64_t seed, int
     return OFDM_OK;
 }
 
-// ofdm_rx and ofdm_rx_profile (who; profile: the record, or null for ofdm_rx)
-static int rx_call(const char* who, ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni,
-                   uint64_t seed, const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on,
-                   const uint8_t* bits, int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters,
-                   void* z_out, int64_t z_keep, int64_t* profile) {
+// The argument path of every fused receiver entry point (who): the plan and the common arguments checked
+// in the order callers rely on -- own(): the entry point's own checks, in their place in it -- and the
+// receiver's common arguments filled.  *run: false with OFDM_OK for an empty run (its stream has no
+// samples and no noise power).
+static int rx_args(const char* who, ofdm_plan_t p, const void* y, const double* nr, const double* ni, uint64_t seed,
+                   const ofdm_stats* stats, int64_t total_samples, int32_t noise_on, const uint8_t* bits,
+                   int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters,
+                   const std::function<int()>& own, RxArgs& a, bool* run) {
     const std::string bad = std::string("bad argument to ") + who;
+    *run = false;
     if (!p || !p->has_const) return fail(OFDM_E_INVALID, std::string(who) + " needs a constellation");
     if (p->eq != OFDM_EQ_NONE && !p->has_channel) return fail(OFDM_E_INVALID, "plan has no channel response");
     if (n_sym < 0 || sym0 < 0 || !counters) return fail(OFDM_E_INVALID, bad);
+    if (int rc = own()) return rc;
     if (int rc = stream_bits_ok(p, bits, who)) return rc;
-    if (n_sym == 0) return OFDM_OK;  // an empty run (its stream has no samples and no noise power)
+    if (n_sym == 0) return OFDM_OK;
     if (!y || (noise_on && (!stats || total_samples <= 0))) return fail(OFDM_E_INVALID, bad);
     if ((nr == nullptr) != (ni == nullptr)) return fail(OFDM_E_INVALID, "nr and ni must both be given or both NULL");
-    RxArgs a{};
     fill_common(p, a.c, bits, seed, sym0, n_sym, sym0 + n_sym);
     a.y = y;
     a.nr = nr;
     a.ni = ni;
     a.stats = (const double*)stats;
     a.total_samples = total_samples;
-    a.snr_lin = std::pow(10.0, snr_db / 10.0);
     a.noise_on = noise_on;
     a.n_valid_bits = n_valid_bits;
     a.counters = counters;
+    *run = true;
+    return OFDM_OK;
+}
+
+// ofdm_rx and ofdm_rx_profile (who; profile: the record, or null for ofdm_rx)
+static int rx_call(const char* who, ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni,
+                   uint64_t seed, const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on,
+                   const uint8_t* bits, int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters,
+                   void* z_out, int64_t z_keep, int64_t* profile) {
+    RxArgs a{};
+    bool run;
+    const int rc = rx_args(who, p, y, nr, ni, seed, stats, total_samples, noise_on, bits, sym0, n_sym, n_valid_bits,
+                           counters, [] { return OFDM_OK; }, a, &run);
+    if (!run) return rc;
+    a.snr_lin = std::pow(10.0, snr_db / 10.0);
     a.z_out = z_out;
     a.z_keep = z_out ? z_keep : 0;
     a.flags = OFDM_ENV_FLAGS("OFDM_ABLATE_RX");
@@ -886,27 +905,22 @@ int ofdm_rx_profile(ofdm_plan_t p, void* stream, const void* y, const double* nr
 int ofdm_rx_sweep(ofdm_plan_t p, void* stream, const void* y, uint64_t seed, const ofdm_stats* stats,
                   int64_t total_samples, const double* snr_db, int32_t n_snr, int64_t sym0, int64_t n_sym,
                   int64_t n_valid_bits, uint64_t* counters) {
-    if (!p || !p->has_const) return fail(OFDM_E_INVALID, "ofdm_rx_sweep needs a constellation");
-    if (p->eq != OFDM_EQ_NONE && !p->has_channel) return fail(OFDM_E_INVALID, "plan has no channel response");
-    if (n_sym < 0 || sym0 < 0 || !counters) return fail(OFDM_E_INVALID, "bad argument to ofdm_rx_sweep");
-    if (n_snr < 1 || n_snr > OFDM_MAX_SWEEP_POINTS)
-        return fail(OFDM_E_INVALID, "ofdm_rx_sweep takes 1 to " + std::to_string(OFDM_MAX_SWEEP_POINTS) +
-                                        " SNR points per call, got " + std::to_string(n_snr));
-    if (!snr_db) return fail(OFDM_E_INVALID, "bad argument to ofdm_rx_sweep");
-    for (int k = 0; k < n_snr; ++k)
-        if (!std::isfinite(snr_db[k]))
-            return fail(OFDM_E_INVALID, "ofdm_rx_sweep: SNR point " + std::to_string(k) + " is not finite");
-    if (int rc = stream_bits_ok(p, nullptr, "ofdm_rx_sweep")) return rc;
-    if (n_sym == 0) return OFDM_OK;  // an empty call
-    if (!y || !stats || total_samples <= 0) return fail(OFDM_E_INVALID, "bad argument to ofdm_rx_sweep");
+    const auto points_ok = [&] {
+        if (n_snr < 1 || n_snr > OFDM_MAX_SWEEP_POINTS)
+            return fail(OFDM_E_INVALID, "ofdm_rx_sweep takes 1 to " + std::to_string(OFDM_MAX_SWEEP_POINTS) +
+                                            " SNR points per call, got " + std::to_string(n_snr));
+        if (!snr_db) return fail(OFDM_E_INVALID, "bad argument to ofdm_rx_sweep");
+        for (int k = 0; k < n_snr; ++k)
+            if (!std::isfinite(snr_db[k]))
+                return fail(OFDM_E_INVALID, "ofdm_rx_sweep: SNR point " + std::to_string(k) + " is not finite");
+        return (int)OFDM_OK;
+    };
     RxSweepArgs a{};
-    fill_common(p, a.r.c, nullptr, seed, sym0, n_sym, sym0 + n_sym);
-    a.r.y = y;
-    a.r.stats = (const double*)stats;
-    a.r.total_samples = total_samples;
-    a.r.noise_on = 1;
-    a.r.n_valid_bits = n_valid_bits;
-    a.r.counters = counters;
+    bool run;
+    // (Philox streams, noise always on: no caller bits or normals)
+    const int rc = rx_args("ofdm_rx_sweep", p, y, nullptr, nullptr, seed, stats, total_samples, 1, nullptr, sym0, n_sym,
+                           n_valid_bits, counters, points_ok, a.r, &run);
+    if (!run) return rc;
     a.n_snr = n_snr;
     for (int k = 0; k < n_snr; ++k) a.snr_lin[k] = std::pow(10.0, snr_db[k] / 10.0);  // (as ofdm_rx)
     a.r.snr_lin = a.snr_lin[0];

@@ -7,6 +7,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 
 #include "ofdm_kernels.hpp"
 
@@ -222,19 +223,8 @@ static hipError_t tx_fast(const TxArgs& a, int* grid, hipStream_t s) {
     return tx_launch<R, LOGN, REF ? 0 : FB, -1>(a, grid, s);
 }
 
-// Reference streams (the caller's bits; RX: and normals) on the bench configs' shapes go through the
-// throughput kernels' REF instantiations -- the timed kernels' bodies with the bit and noise source
-// swapped (ref_lane, array normals) -- so the reference's own streams pin the benched FFT / FIR /
-// slicer / count code (tests/test_gpu_ref_streams.py): complex128, OFDM with a cyclic prefix, fixed
-// 64-QAM at N = 1024 (configs b, c) and 256-QAM at N = 4096 (config e), adaptive square-QAM loading
-// at N = 2048 (config d, FB = 1), flat or <= 8-tap channels within the window FIR's reach.
-// Everything else with caller bits takes the generic kernel.
-// Orders above 256 (1024- / 4096-QAM, wide PSK) always do, by the rules below as they stand: upat is
-// false for a side above 16 (adaptive_fast), ref_shape asks for b = FB <= 8, and the FB switch has no
-// case above 8 -- and the ABI refuses such a plan without caller bits before any launcher runs.
-template <typename R, int LOGN>
-constexpr int ref_fb() { return sizeof(R) == 8 ? (LOGN == 10 ? 6 : LOGN == 11 ? 1 : LOGN == 12 ? 8 : 0) : 0; }
-
+// The routing predicates of every fused launcher (TX, RX, the profile's and the sweep's), defined here once.
+//
 // What the adaptive throughput kernels (FB = 1) take: adaptive bit loading over the reference's
 // square-QAM LUTs (upat: orders <= 256), OFDM with a cyclic prefix
 static inline bool adaptive_fast(const TxRxCommon& c) { return c.adaptive && c.upat && !c.scm && !c.zpad && !c.nn; }
@@ -243,13 +233,51 @@ static inline bool adaptive_fast(const TxRxCommon& c) { return c.adaptive && c.u
 static inline bool fixed_fast(const TxRxCommon& c) {
     return !c.adaptive && (!c.nn || c.psk_m > 0) && (c.b % 2 == 0 || c.psk_m > 0);
 }
+// Philox bits and noise and no received-symbol tap: what every throughput receiver needs
+static inline bool philox_streams(const RxArgs& a) {
+    return a.c.bits == nullptr && a.nr == nullptr && a.z_out == nullptr;
+}
 
+// The bench configs' shapes: complex128, OFDM with a cyclic prefix (or none) -- fixed 64-QAM at N = 1024
+// (configs b, c: FB = 6), adaptive square-QAM loading at N = 2048 (config d: FB = 1), fixed 256-QAM at
+// N = 4096 (config e: FB = 8); 0 = no bench shape at this N and precision.  They are the shapes that have
+//   - REF instantiations of k_tx / k_rx (ref_shape: the caller's bits),
+//   - throughput forms of k_rx_prof (ofdm_prof_inst.hpp: Philox streams),
+//   - throughput forms of k_rx_sweep (ofdm_sweep_inst.hpp: the fixed-QAM ones, FB > 1, only).
 template <typename R, int LOGN>
-static bool ref_shape(const TxRxCommon& c) {
+constexpr int ref_fb() { return sizeof(R) == 8 ? (LOGN == 10 ? 6 : LOGN == 11 ? 1 : LOGN == 12 ? 8 : 0) : 0; }
+// fixed square QAM of exactly FB bits, OFDM, cyclic prefix or none (the part of fixed_fast without
+// PSK, SC-OFDM and zero padding, at one order)
+template <int FB>
+static bool bench_fixed_shape(const TxRxCommon& c) {
+    static_assert(FB > 1 && FB % 2 == 0, "a square-QAM order");
+    return !c.adaptive && !c.nn && c.psk_m == 0 && c.b == FB && !c.scm && !c.zpad;
+}
+template <typename R, int LOGN>
+static bool bench_shape(const TxRxCommon& c) {
     constexpr int FB = ref_fb<R, LOGN>();
-    if (FB == 0 || c.bits == nullptr || c.nn || c.scm || c.zpad) return false;
-    if (FB == 1) return adaptive_fast(c);
-    return !c.adaptive && c.psk_m == 0 && c.b == FB;
+    if constexpr (FB == 0) return false;
+    else if constexpr (FB == 1) return adaptive_fast(c);
+    else return bench_fixed_shape<FB>(c);
+}
+
+// Reference streams (the caller's bits; RX: and normals) on a bench shape, flat or <= 8-tap channels
+// within the window FIR's reach, go through the throughput kernels' REF instantiations -- the timed
+// kernels' bodies with the bit and noise source swapped (ref_lane, array normals) -- so the reference's
+// own streams pin the benched FFT / FIR / slicer / count code (tests/test_gpu_ref_streams.py).
+// Everything else with caller bits takes the generic kernel.
+// Orders above 256 (1024- / 4096-QAM, wide PSK) always do, by the rules above as they stand: upat is
+// false for a side above 16 (adaptive_fast), a bench shape has b = FB <= 8, and the FB switch has no
+// case above 8 -- and the ABI refuses such a plan without caller bits before any launcher runs.
+template <typename R, int LOGN>
+static bool ref_shape(const TxRxCommon& c) { return c.bits != nullptr && bench_shape<R, LOGN>(c); }
+
+// c.eq as a compile-time constant: f(std::integral_constant<int, OFDM_EQ_*>)
+template <typename F>
+static hipError_t with_eq(int eq, F f) {
+    if (eq == OFDM_EQ_NONE) return f(std::integral_constant<int, OFDM_EQ_NONE>{});
+    if (eq == OFDM_EQ_ZF) return f(std::integral_constant<int, OFDM_EQ_ZF>{});
+    return f(std::integral_constant<int, OFDM_EQ_MMSE>{});
 }
 
 // Throughput configuration (Philox bits, N >= 64): fixed_fast -> the kernel specialised on the bits
@@ -291,28 +319,35 @@ hipError_t launch_tx(int logn, const TxArgs& a, int* grid, hipStream_t s) {
 #undef OFDM_TX_CASE
 }
 
+// The tail of every fused receiver launch (k_rx, k_rx_prof, k_rx_sweep), after the launcher has sized
+// the layout: `sm` bytes of dynamic LDS opted in, a grid of ceil(n_sym / SPB) workgroups capped at
+// `rounds` rounds of the workgroups resident at once, each then looping over its share of the symbols
+// (rounds = 0, or a runtime that cannot say: uncapped up to kMaxGrid, or OFDM_GRID_RESIDENT's A/B cap),
+// and the launch.
+template <int BLK, int SPB, typename K, typename A>
+static hipError_t rx_go(K fn, size_t sm, int rounds, int64_t n_sym, const A& a, int* grid, hipStream_t s) {
+    const hipError_t e = set_smem(fn, sm);
+    if (e != hipSuccess) return e;
+    const int64_t want = (n_sym + SPB - 1) / SPB;
+    const int res = rounds > 0 ? resident_blocks(fn, BLK, sm) : 0;
+    *grid = res > 0 ? clamp_grid(std::min<int64_t>(want, (int64_t)rounds * res))
+                    : fused_grid(want, OFDM_GRID_RESIDENT > 0 ? resident_blocks(fn, BLK, sm) : 0);
+    hipLaunchKernelGGL(fn, dim3(*grid), dim3(BLK), sm, s, a);
+    return hipGetLastError();
+}
+
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
 static hipError_t rx_launch(const RxArgs& a, int* grid, hipStream_t s) {
     constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV>();
     if ((a.wide != nullptr) != WIDE) return hipErrorInvalidValue;  // (as tx_launch)
     CarveSize lds;
     rx_carve<R, LOGN, EQ, FB, MV>(lds, a.c.words_per_sym, rx_tts<R, LOGN, FB>(a.c.scm), WIDE ? a.c.n_axis : 0);
-    const size_t sm = lds.bytes;
-    if constexpr (FB > 0) {
-        if (sm + rx_static_lds<R, FB>() > kLdsPerCu) return rx_launch<R, LOGN, -1, 0, true>(a, grid, s);
-    } else {
-        if (sm + rx_static_lds<R, FB>() > kLdsPerCu) return kLdsOverflow;  // (as tx_launch)
+    if (lds.bytes + rx_static_lds<R, FB>() > kLdsPerCu) {  // (as tx_launch)
+        if constexpr (FB > 0) return rx_launch<R, LOGN, -1, 0, true>(a, grid, s);
+        else return kLdsOverflow;
     }
-    auto fn = k_rx<R, LOGN, EQ, FB, MV, REF, WIDE>;
-    hipError_t e = set_smem(fn, sm);
-    if (e != hipSuccess) return e;
-    const int64_t want = (a.c.n_sym + Geo<LOGN, BLK>::SPB - 1) / Geo<LOGN, BLK>::SPB;
-    constexpr int ROUNDS = rx_grid_rounds<R, FB, LOGN>();
-    const int res = ROUNDS > 0 ? resident_blocks(fn, BLK, sm) : 0;
-    *grid = res > 0 ? clamp_grid(std::min<int64_t>(want, (int64_t)ROUNDS * res))
-                    : fused_grid(want, OFDM_GRID_RESIDENT > 0 ? resident_blocks(fn, BLK, sm) : 0);
-    hipLaunchKernelGGL(fn, dim3(*grid), dim3(BLK), sm, s, a);
-    return hipGetLastError();
+    return rx_go<BLK, Geo<LOGN, BLK>::SPB>(k_rx<R, LOGN, EQ, FB, MV, REF, WIDE>, lds.bytes,
+                                           rx_grid_rounds<R, FB, LOGN>(), a.c.n_sym, a, grid, s);
 }
 
 // MV: the run-time modem variants (SC-OFDM, zero padding) compiled in.  complex128 builds them as
@@ -320,9 +355,7 @@ static hipError_t rx_launch(const RxArgs& a, int* grid, hipStream_t s) {
 // transform and guard overlap-add spilled the config (b) receiver (~70 dwords at 128 VGPRs)
 template <typename R, int LOGN, int FB, bool MV = true, bool REF = false>
 static hipError_t rx_eq(const RxArgs& a, int* grid, hipStream_t s) {
-    if (a.c.eq == OFDM_EQ_NONE) return rx_launch<R, LOGN, OFDM_EQ_NONE, FB, MV, REF>(a, grid, s);
-    if (a.c.eq == OFDM_EQ_ZF) return rx_launch<R, LOGN, OFDM_EQ_ZF, FB, MV, REF>(a, grid, s);
-    return rx_launch<R, LOGN, OFDM_EQ_MMSE, FB, MV, REF>(a, grid, s);
+    return with_eq(a.c.eq, [&](auto eq) { return rx_launch<R, LOGN, decltype(eq)::value, FB, MV, REF>(a, grid, s); });
 }
 
 // Throughput configuration (Philox bits and noise, no received-symbol tap; N >= 64): fixed_fast ->
@@ -339,7 +372,7 @@ static hipError_t rx_one(const RxArgs& a, int* grid, hipStream_t s) {
             return rx_eq<R, LOGN, ref_fb<R, LOGN>(), ref_fb<R, LOGN>() == 1, true>(a, grid, s);
     }
     if constexpr (LOGN >= kFastMinLogN) {
-        const bool streams = a.c.bits == nullptr && a.nr == nullptr && a.z_out == nullptr;
+        const bool streams = philox_streams(a);
         if (streams && adaptive_fast(a.c)) return rx_eq<R, LOGN, 1>(a, grid, s);
         if (streams && fixed_fast(a.c)) {
 #define OFDM_RX_FB(F)                                                                      \

@@ -141,6 +141,32 @@ def shard(n: int, rank: int, world: int) -> tuple:
     return lo, hi
 
 
+def _world_rank(group) -> tuple:
+    """(world size, rank) of a process group; (1, 0) without one."""
+    if group is None:
+        return 1, 0
+    import torch.distributed as dist
+
+    return dist.get_world_size(group), dist.get_rank(group)
+
+
+@dataclass
+class _Share:
+    """This rank's share [lo, hi) of a run of global OFDM symbols [0, n_sym), and what every kernel
+    call of the run is given."""
+    dev: torch.device
+    stream: object
+    world: int
+    lo: int
+    hi: int
+    samples: int  # of the whole run: n_sym * (N + cp)
+    n_valid: int  # bits compared, of the whole run
+
+    @property
+    def mine(self) -> int:
+        return self.hi - self.lo
+
+
 class LinkEngine:
     def __init__(self, n_fft: int, cp: int, h_raw: np.ndarray, equalizer: int, luts: Sequence[np.ndarray],
                  sc_lut: Optional[np.ndarray] = None, precision: int = B.OFDM_F64,
@@ -233,15 +259,81 @@ class LinkEngine:
                 with torch.cuda.stream(st):
                     self.reserve(n_sym, per_lane, group)
             return
-        world, rank = 1, 0
+        world, rank = _world_rank(group)
+        lo, hi = shard(n_sym, rank, world)
+        bufs = [self._y(hi - lo) for _ in range(runs_in_flight)]
+        del bufs
+
+    # ------------------------------------------------------------------ the schedule's parts
+    def _share(self, n_sym: int, group, n_valid_bits: Optional[int] = None) -> _Share:
+        world, rank = _world_rank(group)
+        lo, hi = shard(n_sym, rank, world)
+        n_valid = self.valid_bits(n_sym) if n_valid_bits is None else int(n_valid_bits)
+        return _Share(self.device(), self.stream(), world, lo, hi, n_sym * (self.n_fft + self.cp), n_valid)
+
+    def _y(self, n_sym: int) -> torch.Tensor:
+        """The kept channel samples of n_sym OFDM symbols."""
+        return torch.empty((max(n_sym, 1), self.ystride), dtype=self.cdtype, device=self.device())
+
+    def _ybytes(self) -> int:
+        """Bytes of y per OFDM symbol."""
+        return self.ystride * (8 if self.cdtype == torch.complex64 else 16)
+
+    @staticmethod
+    def _finish(acc: torch.Tensor, group, dev) -> tuple:
+        """The end of a run: the asynchronous all-reduce of its counters ``acc`` -- off the critical
+        path: the next run's TX does not wait for it, result() does before reading the counters -- and
+        the ``done`` event on the launch stream (result() may be called under another stream)."""
+        work = None
         if group is not None:
             import torch.distributed as dist
 
-            world, rank = dist.get_world_size(group), dist.get_rank(group)
-        lo, hi = shard(n_sym, rank, world)
-        bufs = [torch.empty((max(hi - lo, 1), self.ystride), dtype=self.cdtype, device=self.device())
-                for _ in range(runs_in_flight)]
-        del bufs
+            work = dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=group, async_op=True)
+        done = None
+        if dev.type == "cuda":
+            done = torch.cuda.Event()
+            done.record()
+        return done, work
+
+    def _schedule(self, r: _Share, seed, bits_d, stats, receive, acc, *, group, y_budget, batch, events) -> tuple:
+        """The schedule of run_async and run_sweep_async for this rank's share: the whole shard
+        resident -- one TX, one receive -- or, when its y exceeds ``y_budget`` (or ``batch`` says so),
+        a power pass first (the AWGN power is a whole-stream mean) and then TX + receive per batch;
+        between TX and the first receive the one statistics all-gather, at the end the counters'
+        all-reduce (_finish, whose (done, work) are returned).  ``receive(y, sym0, n, resident)``
+        enqueues the receiver(s) of symbols [sym0, sym0 + n) held in y; TX is timed into ``events``
+        on the resident path only."""
+        stream = r.stream
+
+        def reduce_stats():
+            # one collective on the TX -> RX critical path: every rank gathers all ranks'
+            # ofdm_stats records and reduces them (combine_stats), so all ranks hold the
+            # statistics -- and sigma -- of a single-GPU run, bit for bit
+            # (run with any process group, one rank included: a 1-rank RCCL group exercises the
+            # same collectives, tests/test_gpu_multirank.py)
+            if group is not None:
+                import torch.distributed as dist
+
+                parts = [torch.empty_like(stats) for _ in range(r.world)]
+                dist.all_gather(parts, stats, group=group)
+                combine_stats(stats, parts)
+
+        per_batch = batch or max(1, min(r.mine, y_budget // self._ybytes()))
+        if per_batch >= r.mine:
+            y = self._y(r.mine)
+            self._timed(events, "ofdm_tx", r.mine, lambda: self.tx(stream, bits_d, seed, r.lo, r.mine, y, stats))
+            reduce_stats()
+            receive(y, r.lo, r.mine, True)
+        else:
+            self.tx(stream, bits_d, seed, r.lo, r.mine, None, stats)
+            reduce_stats()
+            scratch = new_stats(r.dev)
+            y = self._y(per_batch)
+            for b0 in range(r.lo, r.hi, per_batch):
+                nb = min(per_batch, r.hi - b0)
+                self.tx(stream, bits_d, seed, b0, nb, y, scratch)
+                receive(y, b0, nb, False)
+        return self._finish(acc, group, r.dev)
 
     # ------------------------------------------------------------------ run
     def run(self, n_sym: int, snr_db: float, **kw) -> LinkStats:
@@ -271,25 +363,15 @@ class LinkEngine:
                   the profile compiled in, every other run the generic receiver; run_pipelined takes
                   no profile.
         """
-        dev = self.device()
-        stream = self.stream()
-        world, rank = 1, 0
-        if group is not None:
-            import torch.distributed as dist
-
-            world, rank = dist.get_world_size(group), dist.get_rank(group)
-        lo, hi = shard(n_sym, rank, world)
-        mine = hi - lo
-        N, cp = self.n_fft, self.cp
-        samples = n_sym * (N + cp)
-        n_valid = self.valid_bits(n_sym) if n_valid_bits is None else int(n_valid_bits)
+        r = self._share(n_sym, group, n_valid_bits)
+        dev, N = r.dev, self.n_fft
 
         bits_d = None
         if bits is not None:
             need = math.ceil(n_sym * self.bps / 8)
             if len(bits) < need:
                 raise ValueError(f"need {need} tx bytes for {n_sym} OFDM symbols, got {len(bits)}")
-            bits_d = self.upload(np.asarray(bits, dtype=np.uint8)[: math.ceil(hi * self.bps / 8) + 1])
+            bits_d = self.upload(np.asarray(bits, dtype=np.uint8)[: math.ceil(r.hi * self.bps / 8) + 1])
         nr_d = ni_d = None
         if normals is not None and noise_on:
             nr_d = self.upload(np.asarray(normals[0], np.float64))
@@ -301,58 +383,19 @@ class LinkEngine:
         counters = acc[:2]
         prof = acc[2:].view(B.PROFILE_ROWS, N) if profile else None
         pkw = {"profile": prof} if profile else {}  # (rx without a profile is called as before)
-        csize = 8 if self.cdtype == torch.complex64 else 16
-        per_batch = batch or max(1, min(mine, y_budget // (self.ystride * csize)))
-        keep = min(keep_symbols, mine)
+        keep = min(keep_symbols, r.mine)
         z_out = torch.empty((keep, N), dtype=self.cdtype, device=dev) if keep else None
 
-        def reduce_stats():
-            # one collective on the TX -> RX critical path: every rank gathers all ranks'
-            # ofdm_stats records and reduces them (combine_stats), so all ranks hold the
-            # statistics -- and sigma -- of a single-GPU run, bit for bit
-            # (run with any process group, one rank included: a 1-rank RCCL group exercises the
-            # same collectives, tests/test_gpu_multirank.py)
-            if group is not None:
-                import torch.distributed as dist
+        def receive(y, sym0, n, resident):
+            zk = keep if sym0 == r.lo else 0  # the tap: the shard's first symbols, so its first batch
+            self._timed(events if resident else None, "ofdm_rx", n, lambda: self.rx(
+                r.stream, y, nr_d, ni_d, seed, stats, r.samples, snr_db, noise_on, bits_d, sym0, n, r.n_valid,
+                counters, z_out if zk else None, zk, **pkw))
 
-                parts = [torch.empty_like(stats) for _ in range(world)]
-                dist.all_gather(parts, stats, group=group)
-                combine_stats(stats, parts)
-
-        if per_batch >= mine:
-            # whole shard resident: one TX, one RX
-            y = torch.empty((max(mine, 1), self.ystride), dtype=self.cdtype, device=dev)
-            self._timed(events, "ofdm_tx", mine, lambda: self.tx(stream, bits_d, seed, lo, mine, y, stats))
-            reduce_stats()
-            self._timed(events, "ofdm_rx", mine, lambda: self.rx(
-                stream, y, nr_d, ni_d, seed, stats, samples, snr_db, noise_on, bits_d, lo, mine, n_valid,
-                counters, z_out, keep, **pkw))
-        else:
-            # power pass first (the AWGN power is a whole-stream mean), then TX+RX per batch
-            self.tx(stream, bits_d, seed, lo, mine, None, stats)
-            reduce_stats()
-            scratch = new_stats(dev)
-            y = torch.empty((per_batch, self.ystride), dtype=self.cdtype, device=dev)
-            for b0 in range(lo, hi, per_batch):
-                nb = min(per_batch, hi - b0)
-                self.tx(stream, bits_d, seed, b0, nb, y, scratch)
-                zk = keep if b0 == lo else 0
-                self.rx(stream, y, nr_d, ni_d, seed, stats, samples, snr_db, noise_on, bits_d, b0, nb,
-                        n_valid, counters, z_out if zk else None, zk, **pkw)
-        work = None
-        if group is not None:
-            import torch.distributed as dist
-
-            # off the critical path: the next run's TX does not wait for this reduction;
-            # result() waits for it before reading the counters
-            work = dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=group, async_op=True)
-        done = None
-        if dev.type == "cuda":
-            done = torch.cuda.Event()
-            done.record()  # on the launch stream: result() may be called under another stream
-        return PendingLink(n_sym, samples, stats, counters, z_out, done, work, prof,
+        done, work = self._schedule(r, seed, bits_d, stats, receive, acc, group=group, y_budget=y_budget,
+                                    batch=batch, events=events)
+        return PendingLink(n_sym, r.samples, stats, counters, z_out, done, work, prof,
                            self.bits_per_subcarrier if profile else None)
-
 
     # ------------------------------------------------------------------ one-pass SNR sweep
     def run_sweep(self, n_sym: int, snr_dbs, **kw) -> list:
@@ -370,11 +413,9 @@ class LinkEngine:
         (``ofdm_rx_sweep``) draws each symbol's noise words once for all points.  The points share
         their noise realisation (common random numbers: a smooth, monotone curve).
 
-        The schedule is :meth:`run_async`'s: the whole shard resident, or a power pass and then
-        TX + sweep-RX per batch; one statistics all-gather per run and one asynchronous all-reduce
-        of the [K][2] counters.  A list longer than B.MAX_SWEEP_POINTS is split into several
-        receiver launches over the same y.  The counts do not depend on the batching, the rank
-        count, the order of the list or how it is split.
+        The schedule is :meth:`run_async`'s (_schedule), with the [K][2] counters all-reduced.  A list
+        longer than B.MAX_SWEEP_POINTS is split into several receiver launches over the same y.  The
+        counts do not depend on the batching, the rank count, the order of the list or how it is split.
 
         Not taken: caller bits or normals, orders above 256, a profile, a received-symbol tap, and
         a plan per point (adaptive loading re-derived per SNR)."""
@@ -383,62 +424,19 @@ class LinkEngine:
             raise ValueError("run_sweep needs at least one SNR point")
         if not all(math.isfinite(q) for q in snrs):
             raise ValueError("run_sweep needs finite SNR points")
-        K = len(snrs)
-        dev = self.device()
-        stream = self.stream()
-        world, rank = 1, 0
-        if group is not None:
-            import torch.distributed as dist
+        r = self._share(n_sym, group, n_valid_bits)
+        stats = new_stats(r.dev)
+        counters = torch.zeros((len(snrs), 2), dtype=torch.int64, device=r.dev)
 
-            world, rank = dist.get_world_size(group), dist.get_rank(group)
-        lo, hi = shard(n_sym, rank, world)
-        mine = hi - lo
-        N, cp = self.n_fft, self.cp
-        samples = n_sym * (N + cp)
-        n_valid = self.valid_bits(n_sym) if n_valid_bits is None else int(n_valid_bits)
-        stats = new_stats(dev)
-        counters = torch.zeros((K, 2), dtype=torch.int64, device=dev)
-        csize = 8 if self.cdtype == torch.complex64 else 16
-        per_batch = batch or max(1, min(mine, y_budget // (self.ystride * csize)))
-
-        def reduce_stats():  # (as run_async)
-            if group is not None:
-                import torch.distributed as dist
-
-                parts = [torch.empty_like(stats) for _ in range(world)]
-                dist.all_gather(parts, stats, group=group)
-                combine_stats(stats, parts)
-
-        def sweep(y, sym0, n):
-            for k0 in range(0, K, B.MAX_SWEEP_POINTS):
-                k1 = min(K, k0 + B.MAX_SWEEP_POINTS)
+        def receive(y, sym0, n, resident):  # (timed per launch on either path)
+            for k0 in range(0, len(snrs), B.MAX_SWEEP_POINTS):
+                k1 = k0 + B.MAX_SWEEP_POINTS
                 self._timed(events, "ofdm_rx_sweep", n, lambda: self.rx_sweep(
-                    stream, y, seed, stats, samples, snrs[k0:k1], sym0, n, n_valid, counters[k0:k1]))
+                    r.stream, y, seed, stats, r.samples, snrs[k0:k1], sym0, n, r.n_valid, counters[k0:k1]))
 
-        if per_batch >= mine:
-            y = torch.empty((max(mine, 1), self.ystride), dtype=self.cdtype, device=dev)
-            self._timed(events, "ofdm_tx", mine, lambda: self.tx(stream, None, seed, lo, mine, y, stats))
-            reduce_stats()
-            sweep(y, lo, mine)
-        else:
-            self.tx(stream, None, seed, lo, mine, None, stats)
-            reduce_stats()
-            scratch = new_stats(dev)
-            y = torch.empty((per_batch, self.ystride), dtype=self.cdtype, device=dev)
-            for b0 in range(lo, hi, per_batch):
-                nb = min(per_batch, hi - b0)
-                self.tx(stream, None, seed, b0, nb, y, scratch)
-                sweep(y, b0, nb)
-        work = None
-        if group is not None:
-            import torch.distributed as dist
-
-            work = dist.all_reduce(counters, op=dist.ReduceOp.SUM, group=group, async_op=True)
-        done = None
-        if dev.type == "cuda":
-            done = torch.cuda.Event()
-            done.record()
-        return PendingSweep(n_sym, samples, stats, counters, done, work)
+        done, work = self._schedule(r, seed, None, stats, receive, counters, group=group, y_budget=y_budget,
+                                    batch=batch, events=events)
+        return PendingSweep(n_sym, r.samples, stats, counters, done, work)
 
     def lane_streams(self, lanes: int) -> list:
         """The current stream and lanes - 1 more, kept per engine (their allocator pools persist:
@@ -474,20 +472,9 @@ class LinkEngine:
         snrs = list(snr_db) if isinstance(snr_db, (list, tuple, np.ndarray)) else [snr_db] * len(seeds)
         if len(snrs) != len(seeds):
             raise ValueError("one SNR per seed")
-        dev = self.device()
-        stream = self.stream()
-        world, rank = 1, 0
-        if group is not None:
-            import torch.distributed as dist
-
-            world, rank = dist.get_world_size(group), dist.get_rank(group)
-        lo, hi = shard(n_sym, rank, world)
-        mine = hi - lo
-        N, cp = self.n_fft, self.cp
-        samples = n_sym * (N + cp)
-        n_valid = self.valid_bits(n_sym)
-        csize = 8 if self.cdtype == torch.complex64 else 16
-        if 2 * max(mine, 1) * self.ystride * csize > y_budget:
+        r = self._share(n_sym, group)
+        dev, lo, mine = r.dev, r.lo, r.mine
+        if 2 * max(mine, 1) * self._ybytes() > y_budget:
             return [self.run_async(n_sym, q, seed=s, group=group, events=events, y_budget=y_budget)
                     for s, q in zip(seeds, snrs)]
 
@@ -504,13 +491,13 @@ class LinkEngine:
             with on(k):
                 st = self.stream()
                 stats = new_stats(dev)
-                y = torch.empty((max(mine, 1), self.ystride), dtype=self.cdtype, device=dev)
+                y = self._y(mine)
                 self._timed(events, "ofdm_tx", mine, lambda: self.tx(st, None, seed, lo, mine, y, stats))
                 work = None
                 if group is not None:
                     import torch.distributed as dist
 
-                    parts = [torch.empty_like(stats) for _ in range(world)]
+                    parts = [torch.empty_like(stats) for _ in range(r.world)]
                     work = (dist.all_gather(parts, stats, group=group, async_op=True), parts)
             return seed, y, stats, work
 
@@ -520,21 +507,14 @@ class LinkEngine:
 
         def rx_on(state, snr, stream):
             seed, y, stats, work = state
-            if work is not None:  # reduce the gathered statistics (as run_async)
+            if work is not None:  # reduce the gathered statistics (as _schedule)
                 work[0].wait()
                 combine_stats(stats, work[1])
             counters = torch.zeros(2, dtype=torch.int64, device=dev)
             self._timed(events, "ofdm_rx", mine, lambda: self.rx(
-                stream, y, None, None, seed, stats, samples, snr, True, None, lo, mine, n_valid, counters))
-            red = None
-            if group is not None:
-                import torch.distributed as dist
-
-                red = dist.all_reduce(counters, op=dist.ReduceOp.SUM, group=group, async_op=True)
-            done = torch.cuda.Event() if dev.type == "cuda" else None
-            if done is not None:
-                done.record()
-            return PendingLink(n_sym, samples, stats, counters, None, done, red)
+                stream, y, None, None, seed, stats, r.samples, snr, True, None, lo, mine, r.n_valid, counters))
+            done, red = self._finish(counters, group, dev)
+            return PendingLink(n_sym, r.samples, stats, counters, None, done, red)
 
         out = []
         cur = tx(0) if seeds else None
@@ -545,18 +525,11 @@ class LinkEngine:
         return out
 
 
-class PendingLink:
-    """Device-side results of one :meth:`LinkEngine.run_async` call."""
+class _Pending:
+    """Device-side results of a run: its statistics record and counters, the ``done`` event of its
+    launch stream and ``work``, its asynchronous counter all-reduce (multi-rank) or None."""
 
-    def __init__(self, n_sym, samples, stats, counters, z_out, done=None, work=None, profile=None,
-                 bits_per_subcarrier=None):
-        self.n_sym, self.samples = n_sym, samples
-        self.stats, self.counters, self.z_out = stats, counters, z_out
-        self.profile, self.bits_per_subcarrier = profile, bits_per_subcarrier
-        self.done = done
-        self.work = work  # the asynchronous counter all-reduce (multi-rank), or None
-
-    def result(self) -> LinkStats:
+    def _wait(self) -> None:
         if self.done is not None:
             self.done.synchronize()
         if self.work is not None:
@@ -564,11 +537,30 @@ class PendingLink:
             self.work = None
             if self.counters.is_cuda:
                 torch.cuda.current_stream().synchronize()
+
+    def _statistics(self) -> dict:
+        """LinkStats' fields from the run's statistics record (the same for every SNR point of a sweep)."""
         st = self.stats.cpu().numpy()
-        cnt = self.counters.cpu().numpy()
-        samples = self.samples
-        avg = st[1] / samples if samples else 0.0
+        avg = st[1] / self.samples if self.samples else 0.0
         papr = float(10 * np.log10(st[2] / avg)) if avg > 0 else float("inf")
+        return dict(num_ofdm_symbols=self.n_sym, power_sum=float(st[0]), x_power_sum=float(st[1]),
+                    x_peak=float(st[2]), samples=self.samples, papr_db=papr)
+
+
+class PendingLink(_Pending):
+    """Device-side results of one :meth:`LinkEngine.run_async` call."""
+
+    def __init__(self, n_sym, samples, stats, counters, z_out, done=None, work=None, profile=None,
+                 bits_per_subcarrier=None):
+        self.n_sym, self.samples = n_sym, samples
+        self.stats, self.counters, self.z_out = stats, counters, z_out
+        self.profile, self.bits_per_subcarrier = profile, bits_per_subcarrier
+        self.done, self.work = done, work
+
+    def result(self) -> LinkStats:
+        self._wait()
+        shared = self._statistics()
+        cnt = self.counters.cpu().numpy()
         z = self.z_out
         prof = None
         if self.profile is not None:
@@ -577,14 +569,11 @@ class PendingLink:
                                      error_power=profile_power(rec), error_power_fx=rec[2:4].copy(),
                                      n_symbols=self.n_sym,
                                      bits_per_subcarrier=self.bits_per_subcarrier)
-        return LinkStats(
-            bit_errors=int(cnt[0]), symbol_errors=int(cnt[1]), num_ofdm_symbols=self.n_sym,
-            power_sum=float(st[0]), x_power_sum=float(st[1]), x_peak=float(st[2]), samples=samples,
-            papr_db=papr, received=None if z is None else z.cpu().numpy().reshape(-1), profile=prof,
-        )
+        return LinkStats(bit_errors=int(cnt[0]), symbol_errors=int(cnt[1]),
+                         received=None if z is None else z.cpu().numpy().reshape(-1), profile=prof, **shared)
 
 
-class PendingSweep:
+class PendingSweep(_Pending):
     """Device-side results of one :meth:`LinkEngine.run_sweep_async` call: the [K][2] counters and
     the run's one statistics record."""
 
@@ -596,11 +585,7 @@ class PendingSweep:
     def result(self) -> list:
         """One LinkStats per SNR point, in the order given: the point's counts and the run's shared
         power / PAPR fields."""
-        # (PendingLink waits for the launch stream and the counter all-reduce and packages the statistics)
-        shared = PendingLink(self.n_sym, self.samples, self.stats, self.counters[0], None, self.done,
-                             self.work).result()
-        self.done = self.work = None
-        cnt = self.counters.cpu().numpy()
-        return [LinkStats(bit_errors=int(c[0]), symbol_errors=int(c[1]), num_ofdm_symbols=self.n_sym,
-                          power_sum=shared.power_sum, x_power_sum=shared.x_power_sum, x_peak=shared.x_peak,
-                          samples=shared.samples, papr_db=shared.papr_db) for c in cnt]
+        self._wait()
+        shared = self._statistics()
+        return [LinkStats(bit_errors=int(c[0]), symbol_errors=int(c[1]), **shared)
+                for c in self.counters.cpu().numpy()]
