@@ -311,6 +311,30 @@ int ofdm_rx_sweep(ofdm_plan_t plan, void* stream, const void* y, uint64_t seed, 
                   int64_t total_samples, const double* snr_db, int32_t n_snr, int64_t sym0, int64_t n_sym,
                   int64_t n_valid_bits, uint64_t* counters);
 
+/* The fused link: transmit and receive symbols [sym0, sym0 + n_sym) in one kernel, without the kept
+ * channel samples ever leaving the registers -- adds to `counters` what ofdm_tx(plan, stream, NULL, seed,
+ * sym0, n_sym, y, ...) into a buffer followed by ofdm_rx(plan, stream, y, NULL, NULL, seed, stats,
+ * total_samples, snr_db, noise_on, NULL, sym0, n_sym, n_valid_bits, counters, NULL, 0) of that buffer
+ * would add.  In throughput mode y is a pure function of (seed, symbol): each wave maps its symbol's
+ * lane block through the LUT and the IFFT exactly as the transmitter does -- the same code, the same
+ * operation order, so the values are the ones ofdm_tx would have stored -- and receives them in place
+ * (noise, FFT, slicer, count: ofdm_rx's arithmetic), the lane block drawn once for both.  Integer
+ * accumulation: the counts do not depend on the grid, the batching or the rank count.
+ *
+ * It writes no statistics: `stats` is read (power_sum scales the noise, as in ofdm_rx) and must hold the
+ * whole stream's record, e.g. from a power pass ofdm_tx(..., y = NULL, stats) over every symbol (and,
+ * with several ranks, their reduction).
+ * A fused form exists for: complex128, n_fft 1024, fixed 64-QAM, OFDM with a cyclic prefix or none, a
+ * one-tap (flat) channel, OFDM_EQ_NONE (the bench's config b).  Any other plan, or an n_valid_bits
+ * short of all the call's bits ((sym0 + n_sym) * bits per OFDM symbol; the fixed-order receivers
+ * compare every bit), returns OFDM_E_INVALID with the reason in ofdm_last_error(), before any launch:
+ * there is no fall-back to another path.  n_sym = 0: an empty call.
+ * counters: device uint64 [2], accumulated.
+ */
+int ofdm_link(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
+              double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym, int64_t n_valid_bits,
+              uint64_t* counters);
+
 #ifdef __cplusplus
 }
 #endif

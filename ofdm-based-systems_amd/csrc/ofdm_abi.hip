@@ -933,4 +933,43 @@ int ofdm_rx_sweep(ofdm_plan_t p, void* stream, const void* y, uint64_t seed, con
     return OFDM_OK;
 }
 
+int ofdm_link(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
+              double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym, int64_t n_valid_bits,
+              uint64_t* counters) {
+    // what has a fused form, each refusal naming its reason (the launcher's link_shape holds the same
+    // conditions on the kernel's arguments); never another path in its place
+    const auto fused_form = [&] {
+        const auto no = [](const std::string& why) {
+            return fail(OFDM_E_INVALID, "ofdm_link: no fused form: " + why + "; use ofdm_tx and ofdm_rx");
+        };
+        if (p->prec != OFDM_F64) return no("the plan is complex64");
+        if (p->L != 1) return no("the channel has " + std::to_string(p->L) + " taps (flat channels only)");
+        if (p->eq != OFDM_EQ_NONE) return no("the plan has an equaliser");
+        if (p->n != 1024 || p->adaptive || !p->separable || p->psk_m != 0 || p->b != 6 || p->single_carrier ||
+            (p->zp && p->cp > 0))
+            return no("the plan is not fixed 64-QAM cyclic-prefix OFDM at n_fft 1024");
+        // (the fixed-order receivers compare every bit and ignore n_valid_bits: a shorter count
+        // cannot be honoured here)
+        if (n_sym > 0 && n_valid_bits < (sym0 + n_sym) * (int64_t)p->bps)
+            return no("n_valid_bits " + std::to_string(n_valid_bits) + " is short of the call's " +
+                      std::to_string((sym0 + n_sym) * (int64_t)p->bps) + " bits");
+        return (int)OFDM_OK;
+    };
+    LinkArgs a{};
+    bool run;
+    // (Philox streams, no y: the registers carry it; rx_args wants a non-null y, never read)
+    const int rc = rx_args("ofdm_link", p, counters, nullptr, nullptr, seed, stats, total_samples, noise_on, nullptr,
+                           sym0, n_sym, n_valid_bits, counters, fused_form, a.r, &run);
+    if (!run) return rc;
+    a.r.y = nullptr;
+    a.r.snr_lin = std::pow(10.0, snr_db / 10.0);
+    a.h = p->h.p;
+    int grid = 0;
+    const hipError_t launch_result = launch_link<double>(p->logn, p->L, a, &grid, (hipStream_t)stream);
+    if (launch_result == hipErrorInvalidValue) return fail(OFDM_E_INVALID, "ofdm_link: no fused form for this plan");
+    if (launch_result == kLdsOverflow) return lds_overflow(p, "ofdm_link");
+    HIPCHK(launch_result);
+    return OFDM_OK;
+}
+
 }  // extern "C"

@@ -193,6 +193,13 @@ struct RxSweepArgs {
     double snr_lin[OFDM_MAX_SWEEP_POINTS];
 };
 
+// ofdm_link: the receiver's arguments (y, nr / ni, z_out, wide and profile unused) and the channel's
+// one tap, which the transmitter folds into its LUT
+struct LinkArgs {
+    RxArgs r;
+    const void* h;
+};
+
 // complex elements per symbol row of the fused TX: the FFT's padded row, or the extended stream if longer
 constexpr int tx_slot(int logn, int cp, int L) {
     const int ext = (1 << logn) + cp + (L > 1 ? L - 1 : 0);
@@ -241,6 +248,11 @@ hipError_t launch_rx_prof(int logn, const RxArgs& a, int* grid, hipStream_t s);
 // the one-pass SNR sweep receiver (ofdm_sweep_inst.hpp)
 template <typename R>
 hipError_t launch_rx_sweep(int logn, const RxSweepArgs& a, int* grid, hipStream_t s);
+
+// the fused link kernel (ofdm_link_inst.hpp; complex128 only); L: the plan's channel taps.
+// hipErrorInvalidValue: the plan or the arguments have no fused form, nothing was launched
+template <typename R>
+hipError_t launch_link(int logn, int L, const LinkArgs& a, int* grid, hipStream_t s);
 
 hipError_t launch_finalize(const double* partials, int nblocks, int nfields, int max_mask,
                            double* stats, hipStream_t s);

@@ -27,7 +27,8 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib",
 # ABI 5: throughput-mode stream version 3 (the noise radius takes the whole lane word, the phase
 # its own word per four samples; csrc/ofdm_device.hpp "throughput-mode streams")
 # ABI 6: ofdm_rx_profile (the fused receiver with a per-subcarrier error / EVM record)
-# (ofdm_rx_sweep, the one-pass SNR sweep receiver, joined ABI 6 as an added entry point)
+# (ofdm_rx_sweep, the one-pass SNR sweep receiver, joined ABI 6 as an added entry point; so did
+# ofdm_link, the fused transmit + receive kernel)
 ABI_VERSION = 6
 # SNR points one ofdm_rx_sweep call takes (OFDM_MAX_SWEEP_POINTS, include/ofdm_hip.h)
 MAX_SWEEP_POINTS = 40
@@ -115,6 +116,8 @@ SIGNATURES = {
                                        _I64, _VP, _VP, _I64, _VP]),
     # (snr_db: a host array of doubles, copied at the call)
     "ofdm_rx_sweep": (ctypes.c_int, [_VP, _VP, _VP, _U64, _VP, _I64, _c_f64p, _I32, _I64, _I64, _I64, _VP]),
+    # (plan, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits, counters)
+    "ofdm_link": (ctypes.c_int, [_VP, _VP, _U64, _VP, _I64, _F64, _I32, _I64, _I64, _I64, _VP]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -25,6 +25,15 @@ mean, noise/models.py:14, kept as an exact fixed-point sum so that sigma does no
 on the rank count) and one all-reduce of the two u64 counters -- with ``profile=True`` of the
 counters and the per-subcarrier record behind them (integers: the sum is exact).
 
+Fused route (``fused=``, :meth:`LinkEngine.run_async`): where the plan has a fused form -- complex128,
+N = 1024, fixed 64-QAM, cyclic-prefix OFDM, flat channel, no equaliser -- a Philox run is
+
+    ofdm_tx(y = None) : the power pass -- the statistics alone, nothing stored
+    [all-gather of the statistics]
+    ofdm_link         : every symbol transmitted and received in registers -> u64 counters
+
+with no y in HBM at all and the same results bit for bit.
+
 SNR sweeps: :meth:`LinkEngine.run_sweep` transmits once and receives at every SNR of a list in one
 pass (ofdm_rx_sweep); point k is ``run(n_sym, snr_k, seed=seed)``.
 """
@@ -168,6 +177,9 @@ class _Share:
 
 
 class LinkEngine:
+    plan = None    # the libofdm_hip plan (set by __init__)
+    _fused = None  # has_fused, asked of the library once per engine
+
     def __init__(self, n_fft: int, cp: int, h_raw: np.ndarray, equalizer: int, luts: Sequence[np.ndarray],
                  sc_lut: Optional[np.ndarray] = None, precision: int = B.OFDM_F64,
                  prefix: int = B.PREFIX_CYCLIC, modulator: int = B.MOD_OFDM):
@@ -246,6 +258,37 @@ class LinkEngine:
                                         int(total_samples), snrs, len(snr_dbs), int(sym0), int(n_sym),
                                         int(n_valid), B.ptr(counters)))
 
+    def link(self, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid, counters):
+        """ofdm_link: transmit and receive symbols [sym0, sym0 + n_sym) in one kernel, y never leaving
+        the registers; ``stats`` holds the whole stream's record (a power pass, :meth:`tx` with y = None)."""
+        B.check(self._lib.ofdm_link(self.plan.handle, stream, int(seed), B.ptr(stats), int(total_samples),
+                                    float(snr_db), int(noise_on), int(sym0), int(n_sym), int(n_valid),
+                                    B.ptr(counters)))
+
+    @property
+    def has_fused(self) -> bool:
+        """Whether the plan has a fused form (ofdm_link; include/ofdm_hip.h: complex128, N = 1024, fixed
+        64-QAM, cyclic-prefix OFDM, flat channel, no equaliser).  The library decides: an empty
+        ofdm_link call answers for the plan before anything is launched."""
+        if self._fused is None and self.plan is None:
+            self._fused = False  # (no library plan, no library kernel)
+        if self._fused is None:
+            probe = torch.zeros(2, dtype=torch.int64, device=self.device())
+            rc = self._lib.ofdm_link(self.plan.handle, self.stream(), 0, None, 0, 0.0, 0, 0, 0, 0, B.ptr(probe))
+            self._fused = rc == 0
+        return self._fused
+
+    def _route_fused(self, fused: Optional[bool], *, philox: bool, tap: bool, profile: bool, whole: bool) -> bool:
+        """The route of a run: ``fused`` None takes the fused one when the plan has a fused form, the
+        streams are Philox, there is no received-symbol tap, no profile and every bit is compared;
+        False forces the two-kernel path; True raises where no fused form exists."""
+        can = self.has_fused and philox and not tap and not profile and whole
+        if fused and not can:
+            raise ValueError("no fused form for this run: ofdm_link takes a complex128 N = 1024 fixed 64-QAM "
+                             "cyclic-prefix OFDM plan over a flat channel without equaliser, Philox streams, "
+                             "no received-symbol tap, no profile and every bit compared")
+        return can if fused is None else bool(fused)
+
     def reserve(self, n_sym: int, runs_in_flight: int = 2, group=None, lanes: int = 1) -> None:
         """Allocate, and hand back to torch's caching allocator, the channel-sample buffers of
         ``runs_in_flight`` concurrent runs of n_sym global symbols (run_pipelined keeps two
@@ -295,8 +338,12 @@ class LinkEngine:
             done.record()
         return done, work
 
-    def _schedule(self, r: _Share, seed, bits_d, stats, receive, acc, *, group, y_budget, batch, events) -> tuple:
-        """The schedule of run_async and run_sweep_async for this rank's share: the whole shard
+    def _schedule(self, r: _Share, seed, bits_d, stats, receive, acc, *, group, y_budget, batch, events,
+                  link=None) -> tuple:
+        """The schedule of run_async and run_sweep_async for this rank's share: the fused route when
+        ``link`` is given (run_async decided it, _route_fused) -- the power pass ``tx(y=None)`` over the
+        shard, the statistics all-gather, then ``link()``: one ofdm_link over the whole shard, with no y
+        buffer and no batching whatever ``y_budget`` and ``batch`` say -- and otherwise the whole shard
         resident -- one TX, one receive -- or, when its y exceeds ``y_budget`` (or ``batch`` says so),
         a power pass first (the AWGN power is a whole-stream mean) and then TX + receive per batch;
         between TX and the first receive the one statistics all-gather, at the end the counters'
@@ -318,6 +365,11 @@ class LinkEngine:
                 dist.all_gather(parts, stats, group=group)
                 combine_stats(stats, parts)
 
+        if link is not None:
+            self._timed(events, "ofdm_tx", r.mine, lambda: self.tx(stream, bits_d, seed, r.lo, r.mine, None, stats))
+            reduce_stats()
+            link()
+            return self._finish(acc, group, r.dev)
         per_batch = batch or max(1, min(r.mine, y_budget // self._ybytes()))
         if per_batch >= r.mine:
             y = self._y(r.mine)
@@ -344,7 +396,7 @@ class LinkEngine:
                   normals: Optional[tuple] = None, seed: int = 0, noise_on: bool = True, keep_symbols: int = 0,
                   group=None, y_budget: int = DEFAULT_Y_BUDGET, batch: Optional[int] = None,
                   n_valid_bits: Optional[int] = None, events: Optional[list] = None,
-                  profile: bool = False) -> "PendingLink":
+                  profile: bool = False, fused: Optional[bool] = None) -> "PendingLink":
         """Enqueue global OFDM symbols [0, n_sym) (this rank's shard when ``group`` is set) on
         the current stream without waiting for them; :meth:`PendingLink.result` reads the
         counts back.  Back-to-back calls therefore keep the GPU busy while the host prepares
@@ -362,9 +414,17 @@ class LinkEngine:
                   shapes with Philox streams and keep_symbols = 0 run their throughput receiver with
                   the profile compiled in, every other run the generic receiver; run_pipelined takes
                   no profile.
+        fused   : the route.  None: the fused one -- a power pass, then one ofdm_link launch that
+                  transmits and receives every symbol of the shard in registers: no y buffer, no
+                  batching -- when the plan has a fused form (has_fused), the streams are Philox
+                  and there is no tap, no profile and no partial n_valid_bits; the same counts and
+                  statistics, bit for bit.  False: the two-kernel path.  True: ValueError where no
+                  fused form exists.  Events: ("ofdm_tx", ...) for the power pass, ("ofdm_link", ...).
         """
         r = self._share(n_sym, group, n_valid_bits)
         dev, N = r.dev, self.n_fft
+        use_link = self._route_fused(fused, philox=bits is None and normals is None, tap=keep_symbols > 0,
+                                     profile=profile, whole=r.n_valid >= n_sym * self.bps)
 
         bits_d = None
         if bits is not None:
@@ -392,8 +452,12 @@ class LinkEngine:
                 r.stream, y, nr_d, ni_d, seed, stats, r.samples, snr_db, noise_on, bits_d, sym0, n, r.n_valid,
                 counters, z_out if zk else None, zk, **pkw))
 
+        def link():
+            self._timed(events, "ofdm_link", r.mine, lambda: self.link(
+                r.stream, seed, stats, r.samples, snr_db, noise_on, r.lo, r.mine, r.n_valid, counters))
+
         done, work = self._schedule(r, seed, bits_d, stats, receive, acc, group=group, y_budget=y_budget,
-                                    batch=batch, events=events)
+                                    batch=batch, events=events, link=link if use_link else None)
         return PendingLink(n_sym, r.samples, stats, counters, z_out, done, work, prof,
                            self.bits_per_subcarrier if profile else None)
 
@@ -451,7 +515,8 @@ class LinkEngine:
         return [cur] + extra[:lanes - 1]
 
     def run_pipelined(self, n_sym: int, snr_db, seeds, *, group=None,
-                      events: Optional[list] = None, y_budget: int = DEFAULT_Y_BUDGET, lanes: int = 1) -> list:
+                      events: Optional[list] = None, y_budget: int = DEFAULT_Y_BUDGET, lanes: int = 1,
+                      fused: Optional[bool] = None) -> list:
         """Independent throughput-mode runs (one per seed) of global OFDM symbols [0, n_sym),
         software-pipelined across runs: run k+1's TX is enqueued before run k's RX, so with
         several ranks the statistics exchange of run k (the one collective on a run's
@@ -467,15 +532,20 @@ class LinkEngine:
         lanes: HIP streams the runs alternate over (run k on lane k mod lanes, each run's TX,
         exchanges and RX in order on its lane): with 2, one run's receiver overlaps the next run's
         transmitter -- the launch tails and the one-workgroup statistics kernel between them of
-        short runs (a sweep's points) fill with the other lane's work.  One y buffer per lane."""
+        short runs (a sweep's points) fill with the other lane's work.  One y buffer per lane.
+
+        fused: as :meth:`run_async`.  On the fused route a run is a power pass and one ofdm_link
+        launch, pipelined and laned in the same way (run k+1's power pass before run k's link), with
+        no y buffer: ``y_budget`` does not matter."""
         seeds = list(seeds)
         snrs = list(snr_db) if isinstance(snr_db, (list, tuple, np.ndarray)) else [snr_db] * len(seeds)
         if len(snrs) != len(seeds):
             raise ValueError("one SNR per seed")
         r = self._share(n_sym, group)
         dev, lo, mine = r.dev, r.lo, r.mine
-        if 2 * max(mine, 1) * self._ybytes() > y_budget:
-            return [self.run_async(n_sym, q, seed=s, group=group, events=events, y_budget=y_budget)
+        use_link = self._route_fused(fused, philox=True, tap=False, profile=False, whole=True)
+        if not use_link and 2 * max(mine, 1) * self._ybytes() > y_budget:
+            return [self.run_async(n_sym, q, seed=s, group=group, events=events, y_budget=y_budget, fused=False)
                     for s, q in zip(seeds, snrs)]
 
         lane_list = self.lane_streams(lanes) if lanes > 1 and dev.type == "cuda" else None
@@ -491,7 +561,7 @@ class LinkEngine:
             with on(k):
                 st = self.stream()
                 stats = new_stats(dev)
-                y = self._y(mine)
+                y = None if use_link else self._y(mine)  # (fused: the power pass)
                 self._timed(events, "ofdm_tx", mine, lambda: self.tx(st, None, seed, lo, mine, y, stats))
                 work = None
                 if group is not None:
@@ -511,8 +581,12 @@ class LinkEngine:
                 work[0].wait()
                 combine_stats(stats, work[1])
             counters = torch.zeros(2, dtype=torch.int64, device=dev)
-            self._timed(events, "ofdm_rx", mine, lambda: self.rx(
-                stream, y, None, None, seed, stats, r.samples, snr, True, None, lo, mine, r.n_valid, counters))
+            if use_link:
+                self._timed(events, "ofdm_link", mine, lambda: self.link(
+                    stream, seed, stats, r.samples, snr, True, lo, mine, r.n_valid, counters))
+            else:
+                self._timed(events, "ofdm_rx", mine, lambda: self.rx(
+                    stream, y, None, None, seed, stats, r.samples, snr, True, None, lo, mine, r.n_valid, counters))
             done, red = self._finish(counters, group, dev)
             return PendingLink(n_sym, r.samples, stats, counters, None, done, red)
 

@@ -39,6 +39,8 @@ def kernel_key(name: str):
     if ("<float" if PREC == "f32" else "<double") not in name or "<" not in name:
         return None
     args = [a.strip() for a in name[name.index("<") + 1:name.index(">")].split(",")]
+    if "k_link" in name:  # k_link<R, LOGN, FB>: the fused route's second launch (its first is ofdm_tx, y = NULL)
+        return "ofdm_link"
     if "k_rx" in name and len(args) >= 4 and int(args[3]) > 0:  # k_rx<R, LOGN, EQ, FB, MV>
         return "ofdm_rx"
     if "k_tx" in name and len(args) >= 4 and int(args[2]) > 0:  # k_tx<R, LOGN, FB, LT, ZPW>
