@@ -335,6 +335,45 @@ int ofdm_link(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_stats* s
               double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym, int64_t n_valid_bits,
               uint64_t* counters);
 
+/* Edges one ofdm_papr call takes (the kernels hold them, and a bin per edge plus one, in LDS). */
+#define OFDM_MAX_PAPR_EDGES 128
+
+/*
+ * The per-symbol PAPR histogram (an entry point added to ABI 6: nothing of the version's existing
+ * interface changes, so the number stands).  Take global OFDM symbol s.  Its modulated samples are
+ * x_s[0 .. n), n = N + cp: what ofdm_tx's PAPR statistics see -- after the map, and after the
+ * IFFT(ortho) for OFDM (single carrier has no transform); including the cyclic prefix, or the zero
+ * guard, whose zeros count in n and add no power; before the channel.
+ * peak_s = max |x|^2, sum_s = sum |x|^2: lane partials in the arithmetic precision R, reduced over the
+ * symbol's lanes in R.  Then
+ *  - given edges[0 .. K) as linear ratios, strictly increasing, the symbol's bin is
+ *    j = #{ i : (double)peak_s * (double)n >= edges[i] * (double)sum_s }, the comparison evaluated in
+ *    double in both precisions; no logarithm is taken on the device;
+ *  - hist[j] += 1; bin 0 lies below the first edge and bin K at or above the last;
+ *  - a symbol with sum_s = 0 lands in bin K (0 >= 0 holds): the reference's inf;
+ *  - each symbol's pair is computed by the same lanes in the same order for any grid and the counts are
+ *    integers, so the histogram is identical for any grid, batching, sym0 split and rank count.
+ *
+ * bits: as in ofdm_tx -- the caller's bytes of the whole run (reference mode), or NULL (Philox stream
+ *   version 3).
+ * edges: HOST array [n_edges] -- the second host-side array of this ABI, after snr_db -- copied at the
+ *   call into the kernel's arguments (it may be freed or changed once the call returns).
+ * hist: device uint64 [n_edges + 1], accumulated, not zeroed.
+ * sym_out: optional device double [sym_keep][2]: (peak_s, sum_s) of the first min(sym_keep, n_sym)
+ *   symbols of the call, widened from R.
+ * OFDM_E_INVALID, before any launch: a null plan or hist; n_edges outside [1, OFDM_MAX_PAPR_EDGES]; an
+ *   edge that is not finite, not positive or not above its predecessor; bits == NULL on a plan with more
+ *   than 8 bits on a subcarrier (as ofdm_tx); a plan with an order above 256 at all (the wide map is not
+ *   built into k_papr); a layout that does not fit the LDS.  n_sym = 0: an empty call.
+ * It reads no channel taps and writes no ofdm_stats.
+ * Kernels (k_papr): the complex128 cyclic-prefix OFDM fixed-QAM bench shapes (64-QAM at N = 1024,
+ * 256-QAM at N = 4096) with Philox streams a throughput form on the flat transmitter's map and IFFT;
+ * every other plan, and any plan with caller bits, the generic transmitter's.
+ */
+int ofdm_papr(ofdm_plan_t plan, void* stream, const uint8_t* bits, uint64_t seed,
+              int64_t sym0, int64_t n_sym, const double* edges, int32_t n_edges,
+              uint64_t* hist, double* sym_out, int64_t sym_keep);
+
 #ifdef __cplusplus
 }
 #endif

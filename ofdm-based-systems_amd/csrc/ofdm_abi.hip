@@ -972,4 +972,47 @@ int ofdm_link(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stats* stat
     return OFDM_OK;
 }
 
+int ofdm_papr(ofdm_plan_t p, void* stream, const uint8_t* bits, uint64_t seed, int64_t sym0, int64_t n_sym,
+              const double* edges, int32_t n_edges, uint64_t* hist, double* sym_out, int64_t sym_keep) {
+    if (!p || !p->has_const) return fail(OFDM_E_INVALID, "ofdm_papr needs a constellation");
+    if (n_sym < 0 || sym0 < 0 || !hist) return fail(OFDM_E_INVALID, "bad argument to ofdm_papr");
+    if (n_edges < 1 || n_edges > OFDM_MAX_PAPR_EDGES)
+        return fail(OFDM_E_INVALID, "ofdm_papr takes 1 to " + std::to_string(OFDM_MAX_PAPR_EDGES) +
+                                        " edges per call, got " + std::to_string(n_edges));
+    if (!edges) return fail(OFDM_E_INVALID, "bad argument to ofdm_papr");
+    for (int k = 0; k < n_edges; ++k) {
+        if (!std::isfinite(edges[k]) || !(edges[k] > 0.0))
+            return fail(OFDM_E_INVALID, "ofdm_papr: edge " + std::to_string(k) + " is not a finite positive ratio");
+        if (k > 0 && !(edges[k] > edges[k - 1]))
+            return fail(OFDM_E_INVALID, "ofdm_papr: edge " + std::to_string(k) + " is not above its predecessor "
+                                        "(the edges must be strictly increasing)");
+    }
+    if (int rc = stream_bits_ok(p, bits, "ofdm_papr")) return rc;
+    // (after stream_bits_ok: without caller bits a wide plan answers as ofdm_tx does)
+    if (p->wide_plan)
+        return fail(OFDM_E_INVALID, "ofdm_papr: the plan has a constellation above 256 points, and the wide map is "
+                                    "not built into k_papr (orders up to 256 only)");
+    if (n_sym == 0) return OFDM_OK;
+    PaprArgs a{};
+    a.n_edges = n_edges;
+    std::memcpy(a.edges, edges, sizeof(double) * (size_t)n_edges);
+    // a workgroup counts its symbols in 32-bit bins: launches of at most 2^31 symbols
+    const int64_t kMaxLaunch = (int64_t)1 << 31;
+    for (int64_t done = 0; done < n_sym; done += kMaxLaunch) {
+        const int64_t n = std::min(kMaxLaunch, n_sym - done);
+        // the bits buffer covers global symbols [0, sym0 + n_sym)
+        fill_common(p, a.c, bits, seed, sym0 + done, n, sym0 + n_sym);
+        a.hist = (unsigned long long*)hist;
+        a.sym_out = (sym_out && sym_keep > done) ? sym_out + 2 * done : nullptr;
+        a.sym_keep = a.sym_out ? sym_keep - done : 0;
+        int grid = 0;
+#define CALL(R) launch_papr<R>(p->logn, a, &grid, (hipStream_t)stream)
+        const hipError_t launch_result = DISPATCH(p, CALL);
+#undef CALL
+        if (launch_result == kLdsOverflow) return lds_overflow(p, "ofdm_papr");
+        HIPCHK(launch_result);
+    }
+    return OFDM_OK;
+}
+
 }  // extern "C"

@@ -200,6 +200,17 @@ struct LinkArgs {
     const void* h;
 };
 
+// ofdm_papr: the transmitter's common arguments (no channel, no statistics), the histogram, the optional
+// per-symbol trace and the edges (linear ratios, strictly increasing)
+struct PaprArgs {
+    TxRxCommon c;
+    unsigned long long* hist;  // device uint64[n_edges + 1], accumulated
+    double* sym_out;           // device double[sym_keep][2] (peak, sum), or null
+    int64_t sym_keep;
+    int n_edges;
+    double edges[OFDM_MAX_PAPR_EDGES];
+};
+
 // complex elements per symbol row of the fused TX: the FFT's padded row, or the extended stream if longer
 constexpr int tx_slot(int logn, int cp, int L) {
     const int ext = (1 << logn) + cp + (L > 1 ? L - 1 : 0);
@@ -253,6 +264,11 @@ hipError_t launch_rx_sweep(int logn, const RxSweepArgs& a, int* grid, hipStream_
 // hipErrorInvalidValue: the plan or the arguments have no fused form, nothing was launched
 template <typename R>
 hipError_t launch_link(int logn, int L, const LinkArgs& a, int* grid, hipStream_t s);
+
+// the per-symbol PAPR histogram (ofdm_papr_inst.hpp); a plan with an order above 256 is refused by
+// the ABI before it
+template <typename R>
+hipError_t launch_papr(int logn, const PaprArgs& a, int* grid, hipStream_t s);
 
 hipError_t launch_finalize(const double* partials, int nblocks, int nfields, int max_mask,
                            double* stats, hipStream_t s);

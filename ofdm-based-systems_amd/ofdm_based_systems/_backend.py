@@ -32,6 +32,8 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib",
 ABI_VERSION = 6
 # SNR points one ofdm_rx_sweep call takes (OFDM_MAX_SWEEP_POINTS, include/ofdm_hip.h)
 MAX_SWEEP_POINTS = 40
+# edges one ofdm_papr call takes (OFDM_MAX_PAPR_EDGES; ofdm_papr joined ABI 6 as an added entry point too)
+MAX_PAPR_EDGES = 128
 
 OFDM_F32, OFDM_F64 = 0, 1
 # ofdm_stats (include/ofdm_hip.h): power_sum, x_power_sum, x_peak (double), power_fx[2] (int64)
@@ -118,6 +120,9 @@ SIGNATURES = {
     "ofdm_rx_sweep": (ctypes.c_int, [_VP, _VP, _VP, _U64, _VP, _I64, _c_f64p, _I32, _I64, _I64, _I64, _VP]),
     # (plan, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits, counters)
     "ofdm_link": (ctypes.c_int, [_VP, _VP, _U64, _VP, _I64, _F64, _I32, _I64, _I64, _I64, _VP]),
+    # (plan, stream, bits, seed, sym0, n_sym, edges, n_edges, hist, sym_out, sym_keep; edges: a host
+    # array of doubles, copied at the call)
+    "ofdm_papr": (ctypes.c_int, [_VP, _VP, _VP, _U64, _I64, _I64, _c_f64p, _I32, _VP, _VP, _I64]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

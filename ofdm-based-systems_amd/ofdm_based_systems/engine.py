@@ -36,6 +36,10 @@ with no y in HBM at all and the same results bit for bit.
 
 SNR sweeps: :meth:`LinkEngine.run_sweep` transmits once and receives at every SNR of a list in one
 pass (ofdm_rx_sweep); point k is ``run(n_sym, snr_k, seed=seed)``.
+
+PAPR distribution: :meth:`LinkEngine.papr` bins the per-symbol PAPR of the stream ``run`` transmits
+(ofdm_papr: the transmitter's map and IFFT, no channel, no receiver) into an integer histogram on the
+device; :class:`PaprStats` carries it and its CCDF.
 """
 
 from __future__ import annotations
@@ -102,6 +106,43 @@ class LinkStats:
     received: Optional[np.ndarray] = None
     timings: dict = field(default_factory=dict)
     profile: Optional[SubcarrierProfile] = None  # run(..., profile=True)
+
+
+def default_papr_edges_db() -> np.ndarray:
+    """The default edge grid of :meth:`LinkEngine.papr`: -0.125 + 0.25 j dB, j < 64.  It keeps 0 dB out
+    of the edge set: constant-envelope waveforms sit at exactly 0 dB, and an edge there would be
+    decided by rounding."""
+    return -0.125 + 0.25 * np.arange(64, dtype=np.float64)
+
+
+@dataclass
+class PaprStats:
+    """The distribution of the per-symbol PAPR of a run (``ofdm_papr``, include/ofdm_hip.h), binned on
+    the device in integers: identical for any batching and rank count.  Bin j counts the symbols whose
+    ratio peak * n / sum lies in [edge j-1, edge j); bin 0 lies below the first edge, bin K at or
+    above the last (a symbol without power among them)."""
+    edges_db: np.ndarray                     # float64 [K], strictly increasing
+    histogram: np.ndarray                    # int64 [K + 1]; sums to num_ofdm_symbols
+    num_ofdm_symbols: int
+    per_symbol: Optional[np.ndarray] = None  # float64 (keep, 2): (max |x|^2, sum |x|^2) of the kept symbols
+    samples_per_symbol: int = 0              # n = N + cp (the prefix or the zero guard counts)
+
+    @property
+    def ccdf(self) -> np.ndarray:
+        """float64 [K]: ccdf[i] = sum_{j > i} histogram[j] / S = P(ratio >= edge i)."""
+        h = np.asarray(self.histogram, dtype=np.int64)
+        above = np.cumsum(h[::-1])[::-1][1:]
+        return above.astype(np.float64) / max(int(self.num_ofdm_symbols), 1)
+
+    @property
+    def papr_db_per_symbol(self) -> Optional[np.ndarray]:
+        """10 log10(peak n / sum) of the kept symbols (inf for a symbol without power), or None."""
+        if self.per_symbol is None:
+            return None
+        ps = np.asarray(self.per_symbol, dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio = np.where(ps[:, 1] > 0, ps[:, 0] * self.samples_per_symbol / ps[:, 1], np.inf)
+            return 10.0 * np.log10(ratio)
 
 
 def new_stats(dev) -> torch.Tensor:
@@ -264,6 +305,61 @@ class LinkEngine:
         B.check(self._lib.ofdm_link(self.plan.handle, stream, int(seed), B.ptr(stats), int(total_samples),
                                     float(snr_db), int(noise_on), int(sym0), int(n_sym), int(n_valid),
                                     B.ptr(counters)))
+
+    def papr_hist(self, stream, bits_d, seed, sym0, n_sym, edges, hist, sym_out=None, sym_keep=0):
+        """ofdm_papr: bin the per-symbol PAPR of symbols [sym0, sym0 + n_sym) at ``edges`` (linear ratios,
+        strictly increasing, at most B.MAX_PAPR_EDGES: a host list copied at the call) into ``hist``
+        (device int64 [len(edges) + 1], accumulated); sym_out: device float64 (sym_keep, 2) or None."""
+        e = (ctypes.c_double * len(edges))(*[float(q) for q in edges])
+        B.check(self._lib.ofdm_papr(self.plan.handle, stream, B.ptr(bits_d), int(seed), int(sym0), int(n_sym),
+                                    e, len(edges), B.ptr(hist), B.ptr(sym_out), int(sym_keep)))
+
+    def papr(self, n_sym: int, *, seed: int = 0, bits: Optional[np.ndarray] = None, edges_db=None,
+             keep: int = 0, group=None, batch: Optional[int] = None, events: Optional[list] = None) -> PaprStats:
+        """The distribution of the per-symbol PAPR over global OFDM symbols [0, n_sym) of the stream
+        :meth:`run` transmits with the same ``seed`` (or ``bits``: the packed tx bytes of the whole
+        run, reference mode): the modulated samples before the channel, prefix or zero guard
+        included (include/ofdm_hip.h: the definition).  No receiver, no channel, nothing in HBM but the
+        histogram.
+
+        edges_db : strictly increasing edges in dB (default: :func:`default_papr_edges_db`), converted
+                   to ratios on the host as 10 ** (edges_db / 10); at most B.MAX_PAPR_EDGES
+        keep     : keep (max |x|^2, sum |x|^2) of the first ``keep`` symbols of this rank's shard
+                   (PaprStats.per_symbol)
+        batch    : symbols per launch (default: one launch over the shard)
+        group    : the rank's shard of [0, n_sym) is processed here, and the int64 histograms are
+                   all-reduced over the group, as the counters are: every rank holds the whole run's
+        events   : if a list, ("ofdm_papr", n_symbols, start, end) HIP events are appended per launch
+        """
+        edb = default_papr_edges_db() if edges_db is None else np.asarray(edges_db, dtype=np.float64).reshape(-1)
+        edges = 10.0 ** (edb / 10.0)
+        r = self._share(n_sym, group)
+        bits_d = None
+        if bits is not None:
+            need = math.ceil(n_sym * self.bps / 8)
+            if len(bits) < need:
+                raise ValueError(f"need {need} tx bytes for {n_sym} OFDM symbols, got {len(bits)}")
+            bits_d = self.upload(np.asarray(bits, dtype=np.uint8)[: math.ceil(r.hi * self.bps / 8) + 1])
+        hist = torch.zeros(len(edges) + 1, dtype=torch.int64, device=r.dev)
+        kept = max(0, min(int(keep), r.mine))
+        sym_out = torch.zeros((kept, 2), dtype=torch.float64, device=r.dev) if kept else None
+        per_batch = max(1, int(batch)) if batch else max(r.mine, 1)
+        for b0 in range(r.lo, r.hi, per_batch):
+            nb = min(per_batch, r.hi - b0)
+            off = b0 - r.lo  # the trace: the shard's first symbols, so its first batches
+            so = sym_out[off:] if kept > off else None
+            self._timed(events, "ofdm_papr", nb, lambda: self.papr_hist(
+                r.stream, bits_d, seed, b0, nb, edges, hist, so, kept - off if so is not None else 0))
+        if r.mine == 0:  # (an empty shard still answers for the arguments)
+            self.papr_hist(r.stream, bits_d, seed, r.lo, 0, edges, hist, None, 0)
+        done, work = self._finish(hist, group, r.dev)
+        pend = _Pending()
+        pend.done, pend.work, pend.counters = done, work, hist
+        pend._wait()
+        return PaprStats(edges_db=edb.copy(), histogram=hist.cpu().numpy().astype(np.int64),
+                         num_ofdm_symbols=int(n_sym),
+                         per_symbol=None if sym_out is None else sym_out.cpu().numpy(),
+                         samples_per_symbol=self.n_fft + self.cp)
 
     @property
     def has_fused(self) -> bool:

@@ -137,8 +137,16 @@ class Simulation:
         make_plot: bool = True,
         process_group=None,
         subcarrier_profile: bool = False,
+        papr_ccdf: bool = False,
+        papr_edges_db=None,
     ):
-        """subcarrier_profile: also return the run's per-subcarrier results, accumulated on the GPU over
+        """papr_ccdf: also return the distribution of the per-symbol PAPR of the transmitted stream,
+        binned on the GPU over every OFDM symbol (engine.PaprStats, ``LinkEngine.papr``): the key
+        ``papr_ccdf`` = {``edges_db``, ``ccdf``, ``histogram``, ``num_ofdm_symbols``} as lists, at
+        ``papr_edges_db`` (default: -0.125 + 0.25 j dB, j < 64).  Without it the result dict is
+        unchanged.  Needs the fused path, and constellation orders up to 256.
+
+        subcarrier_profile: also return the run's per-subcarrier results, accumulated on the GPU over
         every OFDM symbol (engine.SubcarrierProfile): the keys ``bit_errors_per_subcarrier``,
         ``symbol_errors_per_subcarrier``, ``error_power_per_subcarrier`` (sum of |z - c|^2 against the
         transmitted point) and ``mer_db_per_subcarrier``.  Without it the result dict is unchanged.
@@ -178,6 +186,8 @@ class Simulation:
         self.make_plot = make_plot
         self.process_group = process_group
         self.subcarrier_profile = subcarrier_profile
+        self.papr_ccdf = papr_ccdf
+        self.papr_edges_db = papr_edges_db
 
     def _log(self, message: str) -> None:
         if self.verbose:
@@ -431,6 +441,8 @@ class Simulation:
             raise ValueError("rng_mode='philox' needs the built-in modulators, prefixes and constellations")
         if not fused and self.subcarrier_profile:
             raise ValueError("subcarrier_profile needs the built-in modulators, prefixes and constellations")
+        if not fused and self.papr_ccdf:
+            raise ValueError("papr_ccdf needs the built-in modulators, prefixes and constellations")
         if not fused and link is not None:
             raise ValueError("run_sweep needs the fused path (channel order and prefix within n_fft)")
         t0 = time.perf_counter()
@@ -451,10 +463,17 @@ class Simulation:
             if link is not None:
                 st = link(make_engine, n_ofdm_syms, seed, valid_bits)
             else:
-                st = make_engine().run(n_ofdm_syms, self.snr_db, bits=tx_bytes, normals=normals, seed=seed,
-                                       noise_on=noise_on, keep_symbols=self.received_symbols_keep,
-                                       group=self.process_group, batch=self.batch_symbols,
-                                       n_valid_bits=valid_bits, profile=self.subcarrier_profile)
+                eng = make_engine()
+                st = eng.run(n_ofdm_syms, self.snr_db, bits=tx_bytes, normals=normals, seed=seed,
+                             noise_on=noise_on, keep_symbols=self.received_symbols_keep,
+                             group=self.process_group, batch=self.batch_symbols,
+                             n_valid_bits=valid_bits, profile=self.subcarrier_profile)
+            if self.papr_ccdf:
+                # the per-symbol PAPR distribution of the stream just transmitted: the same plan, seed
+                # and (reference mode) the run's own bits
+                papr = (eng if link is None else make_engine()).papr(
+                    n_ofdm_syms, seed=seed, bits=tx_bytes, edges_db=self.papr_edges_db,
+                    group=self.process_group, batch=self.batch_symbols)
             torch.cuda.synchronize()
             bit_errors, symbol_errors, papr_db = st.bit_errors, st.symbol_errors, st.papr_db
             received = st.received if st.received is not None else np.zeros(0, np.complex128)
@@ -483,6 +502,13 @@ class Simulation:
                 "error_power_per_subcarrier": profile.error_power,
                 "mer_db_per_subcarrier": profile.mer_db,
             })
+        if self.papr_ccdf:
+            results["papr_ccdf"] = {
+                "edges_db": papr.edges_db.tolist(),
+                "ccdf": papr.ccdf.tolist(),
+                "histogram": papr.histogram.tolist(),
+                "num_ofdm_symbols": papr.num_ofdm_symbols,
+            }
         results["constellation_plot"] = self._plot(received, mapper, ber, papr_db, results["title"], orders)
         results["transmission_time_ms"] = elapsed * 1000
         results["bitrate_mbps"] = total_bits / 1e6  # the reference reports Mbit, not a rate (:807)
