@@ -330,10 +330,37 @@ int ofdm_rx_sweep(ofdm_plan_t plan, void* stream, const void* y, uint64_t seed, 
  * compare every bit), returns OFDM_E_INVALID with the reason in ofdm_last_error(), before any launch:
  * there is no fall-back to another path.  n_sym = 0: an empty call.
  * counters: device uint64 [2], accumulated.
+ * The float32 screen (ofdm_link_screen below) runs in its automatic mode; the counts are the same in
+ * every mode.
  */
 int ofdm_link(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
               double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym, int64_t n_valid_bits,
               uint64_t* counters);
+
+/* Modes of the fused link's float32 screen. */
+#define OFDM_LINK_SCREEN_AUTO 0   /* the kernel decides from sigma and the level spacing (ofdm_link) */
+#define OFDM_LINK_SCREEN_OFF 1    /* every symbol in complex128: the unscreened kernel (for A/B) */
+#define OFDM_LINK_SCREEN_FORCED 2 /* every symbol screened, whatever the SNR */
+
+/*
+ * ofdm_link with the screen's mode and counts (an entry point added to ABI 6: nothing of the version's
+ * existing interface changes, so the number stands).  The fused kernel reports integer decisions only,
+ * and a decision needs complex128 only when the received point lies within rounding distance of a
+ * slicer boundary.  A screened wave runs its symbol in float32 first and proves, per element and axis,
+ * that the level coordinate is further from every decision boundary than a rigorous bound on the
+ * distance between the float32 and the float64 coordinate of this symbol; if any element fails, the wave
+ * redoes the whole symbol in complex128.  Either way the decisions are the complex128 ones: `counters`
+ * receives exactly what ofdm_link's complex128 arithmetic adds, in every mode and for any share redone.
+ * Automatic mode screens when the noise is off or the expected share of undecided symbols is small
+ * (64-QAM: from about 22 dB up), a decision made once per launch from sigma and the level spacing.
+ * mode: OFDM_LINK_SCREEN_AUTO, _OFF or _FORCED; anything else is OFDM_E_INVALID.
+ * screen_counts: optional device uint64 [2], accumulated: symbols screened, and symbols of those redone
+ *   in complex128 (both stay as they are when the screen is off).
+ * Everything else -- arguments, refusals, no fall-back -- as ofdm_link.
+ */
+int ofdm_link_screen(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_stats* stats,
+                     int64_t total_samples, double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym,
+                     int64_t n_valid_bits, uint64_t* counters, int32_t mode, uint64_t* screen_counts);
 
 /* Edges one ofdm_papr call takes (the kernels hold them, and a bin per edge plus one, in LDS). */
 #define OFDM_MAX_PAPR_EDGES 128

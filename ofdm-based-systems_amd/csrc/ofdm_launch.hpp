@@ -194,10 +194,13 @@ struct RxSweepArgs {
 };
 
 // ofdm_link: the receiver's arguments (y, nr / ni, z_out, wide and profile unused) and the channel's
-// one tap, which the transmitter folds into its LUT
+// one tap, which the transmitter folds into its LUT; ofdm_link_screen: the screen's mode
+// (OFDM_LINK_SCREEN_*; ofdm_link: automatic) and its counts
 struct LinkArgs {
     RxArgs r;
     const void* h;
+    int mode;
+    unsigned long long* screen_counts;  // device uint64[2] (symbols screened, symbols redone), accumulated, or null
 };
 
 // ofdm_papr: the transmitter's common arguments (no channel, no statistics), the histogram, the optional

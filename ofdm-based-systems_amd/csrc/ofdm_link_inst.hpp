@@ -13,6 +13,17 @@
 //
 // Shape: complex128, fixed square QAM of FB bits, cyclic-prefix OFDM (or no prefix), flat channel,
 // Philox streams, no equaliser -- bench config (b) at N = 1024, FB = 6.
+//
+// SCREEN (ofdm_link's automatic mode, ofdm_link_screen): the kernel reports integer decisions only, and a
+// decision needs complex128 only when the received point lies within rounding distance of a slicer
+// boundary.  Each wave first runs its symbol in float32 on the complex64 kernels' templates (the float
+// LUT gather, fft_sym<float>, Mwc64x::add_noise, PermSlicer's two packed FMAs) and proves, per element
+// and axis, that the level coordinate is further from every half-integer boundary than delta, a
+// rigorous bound on the distance between the float32 and the float64 coordinate of this symbol
+// (screen_bound below).  One ballot: every element decisive -> the float32 XOR /
+// popcount is the symbol's count (the levels are the float64 path's, so the words are); otherwise the
+// wave re-seeds and redoes the whole symbol on the complex128 statements, unchanged.  The counts are
+// the unscreened kernel's whatever share is redone.
 #pragma once
 
 #include "ofdm_kernels_inst.hpp"
@@ -36,25 +47,118 @@ struct LinkLds {
     AxisInfo* axis;
     unsigned char* rowmem;
     unsigned long long* redc;
+    // SCREEN: the same twiddles [forward | inverse] and the folded LUT rounded to float32
+    cpx<float>* tt32;
+    cpx<float>* lut32;
 };
-template <typename R, int LOGN, typename CV>
+template <typename R, int LOGN, bool SCREEN = false, int FB = 0, typename CV>
 __host__ __device__ __forceinline__ constexpr LinkLds<R> link_carve(CV& cv) {
     using G = Geo<LOGN, OFDM_LINK_BLOCK>;
     LinkLds<R> m{};
     m.axis = cv.template take<AxisInfo>(kMaxLuts);
+    // (PADN complex64 take what PADN doubles take: the float32 transforms exchange through the same row)
     m.rowmem = cv.template take<unsigned char>((size_t)G::SPB * G::PADN * sizeof(R));
     m.redc = cv.template take<unsigned long long>(OFDM_LINK_BLOCK / 64);
     m.tt = cv.template take<cpx<R>>(2 * tt_size(LOGN));
+    m.tt32 = cv.template take<cpx<float>>(SCREEN ? 2 * tt_size(LOGN) : 0);
+    m.lut32 = cv.template take<cpx<float>>(SCREEN ? (1 << FB) : 0);
     return m;
 }
 // static LDS: the transmitter's LUT, the noise phase table and its widening to double
 template <typename R, int FB>
 constexpr size_t link_static_lds() { return (1 << FB) * sizeof(cpx<R>) + rx_static_lds<R, FB>(); }
 
-template <typename R, int LOGN, int FB>
+// ---- the screen's bound (DESIGN.md section 4 has the derivation)
+// u = 2^-24, the float32 unit roundoff.  Higham, Accuracy and Stability of Numerical Algorithms, Theorem
+// 24.2: a transform of t = log2 N radix-2 levels with twiddles off by mu has a relative 2-norm error
+// of at most t eta / (1 - t eta), eta = mu + gamma_4 (sqrt 2 + mu).  The 16.16.4 passes are 10 such
+// levels with fewer products than radix 2 has (4 on a path), and the twiddles, the w16 constants and
+// the LUT are float64 values rounded once (mu <= u): eta <= 6.66 u, 66.6 u per transform.  With the
+// LUT's rounding and the noise FMA's (one u each) the received spectrum z of a symbol obeys
+//   |z32_k - z64_k| <= ||z32 - z64||_2 <= kScreenK u (||z32||_2 + sqrt N ||x||_2),  kScreenK = 70,
+// x the transmitted samples, ||x||_2 <= N a with a the largest modulus of the folded LUT (1 / sqrt N
+// inside); 70 over 67.6 covers the 1 / (1 - t eta), the second-order terms, the float64 side's 2^-53
+// ones and the float32 evaluation of the norm and of this bound.
+constexpr double kScreenK = 70.0;
+constexpr double kScreenU = 0x1p-24;
+// the level coordinate's own roundings, in levels: the slicer's two constants and its first FMA
+// ((0.6 + 0.5 + 1) u of the clamped coordinate, times side - 1 <= 15), and the margin's FMA
+constexpr double kScreenSlicerU = 40.0;
+// automatic mode: screen when the expected number of undecided axes of a symbol is below this (a
+// share 1 - exp(-0.35) = 0.30 of the symbols redone; the screen pays below about 0.4)
+constexpr double kScreenMaxUndecided = 0.35;
+
+// PermSlicer with the decision's margin: m = max(m, |y - round(y)|) over both axes of the four elements,
+// y the clamped level coordinate -- 1/2 - m is the distance to the nearest decision boundary (a clamped
+// end gives y = round(y): never near one).
+template <int FB>
+struct ScreenSlicer : PermSlicer<FB> {
+    using P = PermSlicer<FB>;
+    __device__ void load(const AxisInfo& a, double scale) {
+        P::load(a, (float)scale);
+        // the level multiplier rounded once from the double product (P::load rounds the scale first)
+        const float is = (float)(a.inv_step * scale / (double)(P::SIDE - 1));
+        this->mul = f32x2{is, is};
+    }
+    __device__ __forceinline__ uint32_t diff_margin(const cpx<float> (&z)[4], uint32_t txw, float& m) const {
+        uint32_t li[4], lq[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            f32x2 v;
+            asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(v) : "v"(z[j].v), "v"(this->mul), "v"(this->add));
+            uint64_t fb;
+            asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(fb) : "v"(v), "v"(this->smax), "v"(this->magic));
+            li[j] = (uint32_t)fb;
+            lq[j] = (uint32_t)(fb >> 32);
+            // round(y) = the magic sum less the magic, exact; y - round(y) in one FMA, per axis in
+            // scalar float (no lane of a packed value is reinterpreted)
+            const float ri = __uint_as_float(li[j]) - 12582912.0f, rq = __uint_as_float(lq[j]) - 12582912.0f;
+            const float ei = __builtin_fmaf(v.x, this->smax.x, -ri), eq = __builtin_fmaf(v.y, this->smax.x, -rq);
+            m = __builtin_fmaxf(m, __builtin_fmaxf(__builtin_fabsf(ei), __builtin_fabsf(eq)));
+        }
+        const uint32_t si = __builtin_amdgcn_perm(__builtin_amdgcn_perm(li[3], li[2], 0x0c0c0400u),
+                                                  __builtin_amdgcn_perm(li[1], li[0], 0x0c0c0400u), 0x05040100u);
+        const uint32_t sq = __builtin_amdgcn_perm(__builtin_amdgcn_perm(lq[3], lq[2], 0x0c0c0400u),
+                                                  __builtin_amdgcn_perm(lq[1], lq[0], 0x0c0c0400u), 0x05040100u);
+        return (P::lookup(this->ti, si) | P::lookup(this->tq, sq)) ^ (txw & P::BYTE_MASK);
+    }
+};
+
+// The screen's constants of a launch: delta in levels = cz ||z32||_2 + c0 (screen_bound above times
+// the level multiplier, plus the slicer's own roundings), and the expected undecided axes per symbol.
+struct ScreenConst {
+    float cz, c0;
+    double undecided;
+};
+// lvl: levels per unit of z (the slicer's multiplier times side - 1); amax: the folded LUT's largest
+// modulus; p: the stream's mean sample power; sigma: the noise's per-component deviation
+template <int LOGN, int FB>
+__host__ __device__ inline ScreenConst screen_const(double lvl, double amax, double p, double sigma) {
+    constexpr double N = (double)(1 << LOGN), side = (double)(1 << (FB / 2));
+    const double rootn = sqrt(N);
+    const double kz = kScreenK * kScreenU * lvl;
+    ScreenConst c;
+    // (1.001: the float rounding of the two constants and of cz sqrt(n2) + c0 itself)
+    c.cz = (float)(1.001 * kz);
+    c.c0 = (float)(1.001 * (kz * N * rootn * amax + kScreenSlicerU * kScreenU));
+    // An axis is undecided when its coordinate lies within delta of one of the side - 1 boundaries;
+    // under noise of deviation sc levels the coordinate's density there is phi(1/2 / sc) / sc from each of
+    // the two levels beside it, each sent with probability 1 / side.  ||z||_2 ~ N sqrt(p + 2 sigma^2).
+    c.undecided = 0.0;
+    if (sigma > 0.0) {
+        const double sc = sigma * rootn * lvl;
+        const double delta = kz * (N * sqrt(p + 2.0 * sigma * sigma) + N * rootn * amax) + kScreenSlicerU * kScreenU;
+        const double phi = exp(-0.125 / (sc * sc)) * 0.3989422804014327 / sc;
+        c.undecided = 2.0 * N * (side - 1.0) * (2.0 / side) * 2.0 * delta * phi;
+    }
+    return c;
+}
+
+template <typename R, int LOGN, int FB, bool SCREEN = false>
 __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkArgs la) {
     static_assert(sizeof(R) == 8 && FB > 1 && !(FB & 1), "complex128 fixed square QAM");
     static_assert(uses_tt<R, LOGN, FB>() && Geo<LOGN>::TPS >= 64, "a symbol per wave, per-pass twiddles in LDS");
+    static_assert(!SCREEN || Geo<LOGN>::TPS == 64, "the screen's ballot and its redo are one wave's");
     constexpr int BLK = OFDM_LINK_BLOCK;
     using G = Geo<LOGN, BLK>;
     using C = cpx<R>;
@@ -66,7 +170,7 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
     __shared__ f32x2 ntab[kNoisePhases];
     __shared__ f64x2 ntab64[kNoisePhases];
     Carve cv(ofdm_smem);
-    const LinkLds<R> lds = link_carve<R, LOGN>(cv);
+    const LinkLds<R> lds = link_carve<R, LOGN, SCREEN, FB>(cv);
     C* tt = lds.tt;
     AxisInfo* axis = lds.axis;
     unsigned long long* redc = lds.redc;
@@ -83,9 +187,11 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
     // sigma from the whole-stream mean power (as k_rx)
     const bool noise = a.noise_on;
     double sigma_d = 0;
+    [[maybe_unused]] double power = 0;
     if (noise) {
         const double p = a.stats[0] / (double)a.total_samples;
         sigma_d = sqrt((p / a.snr_lin) / 2.0);
+        power = p;
     }
     build_noise_table(ntab, sigma_d, ntab64);
     st_tt.store(tt);
@@ -101,47 +207,138 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
     PermSlicer64<FB> pslicer;
     pslicer.load(axis[0], cm.scale);  // the FFT output stays unscaled (x sqrt N)
 
+    // SCREEN: the float32 tables rounded from the staged double ones (what a complex64 plan uploads;
+    // the LUT from the folded one), the slicer, the bound's constants and the workgroup's decision
+    using CF = cpx<float>;
+    [[maybe_unused]] CF* const tt32 = lds.tt32;
+    [[maybe_unused]] CF* const lut32 = lds.lut32;
+    [[maybe_unused]] ScreenSlicer<FB> fslicer;
+    [[maybe_unused]] bool screen = false;
+    [[maybe_unused]] float cz = 0, c0 = 0;
+    if constexpr (SCREEN) {
+        for (int i = threadIdx.x; i < 2 * TTS; i += BLK) tt32[i] = mk<float>((float)tt[i].re, (float)tt[i].im);
+        double amax = 0;
+        for (int i = 0; i < (1 << FB); ++i) {
+            const C v = lut_s[i];
+            amax = fmax(amax, v.re * v.re + v.im * v.im);
+            if (i == (int)threadIdx.x) lut32[i] = mk<float>((float)v.re, (float)v.im);
+        }
+        static_assert((1 << FB) <= BLK, "one LUT entry per thread");
+        fslicer.load(axis[0], cm.scale);
+        const ScreenConst sc = screen_const<LOGN, FB>((double)fslicer.mul.x * (double)(PermSlicer<FB>::SIDE - 1),
+                                                      sqrt(amax), power, sigma_d);
+        cz = sc.cz;
+        c0 = sc.c0;
+        screen = la.mode == OFDM_LINK_SCREEN_FORCED || !noise || sc.undecided < kScreenMaxUndecided;
+        __syncthreads();
+    }
+
     const int64_t niter = (cm.n_sym + G::SPB - 1) / G::SPB;
     unsigned long long be = 0, se = 0;
+    [[maybe_unused]] unsigned long long screened = 0, redone = 0;  // (lane 0 of each wave counts)
     for (int64_t it = blockIdx.x; it < niter; it += gridDim.x) {
         const int64_t sl = it * G::SPB + ls;
         const int64_t sg = cm.sym0 + sl;
         const bool active = sl < cm.n_sym;
-        // the lane block: bits for both halves, the generator continuing into the lane's noise
-        TxBits<FB, TPS> tb;
-        tb.load(cm, sg, t, nullptr, active);
-        // transmitter: map and IFFT; x leaves the IFFT as the channel output y
-        C x[E];
-        static_for<0, E>([&](auto I) { x[I] = lut_s[tb.template fixed<I>()]; });
-        fft_sym<R, LOGN, true, FB>(x, row, tt, tt + TTS, t);
-        sym_sync<TPS>();  // the IFFT's last pass has read the row
-        // receiver: y + AWGN, FFT, slice, compare, count
-        if (active && noise) {
+        [[maybe_unused]] bool redo = true;
+        if constexpr (SCREEN) {
+            if (screen) {
+                redo = false;
+                if (active) {
+                    // the symbol in float32: the complex64 kernels' statements through the same row
+                    CF* const rowf = (CF*)row;
+                    TxBits<FB, TPS> tb;
+                    tb.load(cm, sg, t, nullptr, true);
+                    CF xf[E];
+                    static_for<0, E>([&](auto I) { xf[I] = lut32[tb.template fixed<I>()]; });
+                    fft_sym<float, LOGN, true, FB>(xf, rowf, tt32, tt32 + TTS, t);
+                    sym_sync<TPS>();  // the IFFT's last pass has read the row
+                    if (noise) {
 #pragma unroll
-            for (int i = 0; i < E; ++i) tb.g.add_noise64(x[i].re, x[i].im, ntab64, i);
-        }
-        fft_sym<R, LOGN, false, FB>(x, row, tt, tt, t);
-        if (active) {
-            uint32_t bes = 0, ses = 0;
-            static_for<0, E / 4>([&](auto Q) {
-                constexpr int q = Q;
-                C z[4];
+                        for (int i = 0; i < E; ++i) tb.g.add_noise(xf[i].v, ntab, i);
+                    }
+                    fft_sym<float, LOGN, false, FB>(xf, rowf, tt32, tt32, t);
+                    // delta of this symbol, in levels, from its own norm
+                    f32x2 acc = f32x2{0.f, 0.f};
 #pragma unroll
-                for (int j = 0; j < 4; ++j) z[j] = x[4 * q + j];
-                const uint32_t d = pslicer.diff(z, lane_word(tb.lane, q));
-                bes += __popc(d);
-                ses += PermSlicer<FB>::nonzero_bytes(d);
-            });
-            be += bes;
-            se += ses;
+                    for (int i = 0; i < E; ++i) acc = __builtin_elementwise_fma(xf[i].v, xf[i].v, acc);
+                    float n2 = acc.x + acc.y;
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) n2 += __shfl_xor(n2, off, 64);
+                    // (a delta of 1/2 or more, or a norm that is not finite: nothing is decisive)
+                    const float delta = __builtin_fmaf(cz, __builtin_amdgcn_sqrtf(n2), c0);  // (v_sqrt_f32: 1 ulp)
+                    const float thr = delta < 0.5f ? 0.5f - delta : -1.0f;
+                    uint32_t bes = 0, ses = 0;
+                    float m = 0.f;
+                    static_for<0, E / 4>([&](auto Q) {
+                        constexpr int q = Q;
+                        CF z[4];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) z[j] = xf[4 * q + j];
+                        const uint32_t d = fslicer.diff_margin(z, lane_word(tb.lane, q), m);
+                        bes += __popc(d);
+                        ses += PermSlicer<FB>::nonzero_bytes(d);
+                    });
+                    redo = __ballot(!(m <= thr)) != 0;  // one undecided axis: the wave redoes the symbol
+                    if (!redo) {
+                        be += bes;
+                        se += ses;
+                    }
+                    if (t == 0) {
+                        ++screened;
+                        redone += redo;
+                    }
+                    sym_sync<TPS>();  // the row is rewritten by the redo or the next symbol
+                }
+            }
         }
-        sym_sync<TPS>();  // the FFT row is rewritten by the next symbol
+        if (!SCREEN || redo) {
+            // the lane block: bits for both halves, the generator continuing into the lane's noise
+            TxBits<FB, TPS> tb;
+            tb.load(cm, sg, t, nullptr, active);
+            // transmitter: map and IFFT; x leaves the IFFT as the channel output y
+            C x[E];
+            static_for<0, E>([&](auto I) { x[I] = lut_s[tb.template fixed<I>()]; });
+            fft_sym<R, LOGN, true, FB>(x, row, tt, tt + TTS, t);
+            sym_sync<TPS>();  // the IFFT's last pass has read the row
+            // receiver: y + AWGN, FFT, slice, compare, count
+            if (active && noise) {
+#pragma unroll
+                for (int i = 0; i < E; ++i) tb.g.add_noise64(x[i].re, x[i].im, ntab64, i);
+            }
+            fft_sym<R, LOGN, false, FB>(x, row, tt, tt, t);
+            if (active) {
+                uint32_t bes = 0, ses = 0;
+                static_for<0, E / 4>([&](auto Q) {
+                    constexpr int q = Q;
+                    C z[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) z[j] = x[4 * q + j];
+                    const uint32_t d = pslicer.diff(z, lane_word(tb.lane, q));
+                    bes += __popc(d);
+                    ses += PermSlicer<FB>::nonzero_bytes(d);
+                });
+                be += bes;
+                se += ses;
+            }
+            sym_sync<TPS>();  // the FFT row is rewritten by the next symbol
+        }
     }
     be = block_sum<unsigned long long, BLK>(be, redc);
     se = block_sum<unsigned long long, BLK>(se, redc);
     if (threadIdx.x == 0) {
         if (be) atomicAdd((unsigned long long*)&a.counters[0], be);
         if (se) atomicAdd((unsigned long long*)&a.counters[1], se);
+    }
+    if constexpr (SCREEN) {
+        if (la.screen_counts) {  // (launch-uniform)
+            screened = block_sum<unsigned long long, BLK>(screened, redc);
+            redone = block_sum<unsigned long long, BLK>(redone, redc);
+            if (threadIdx.x == 0) {
+                if (screened) atomicAdd(&la.screen_counts[0], screened);
+                if (redone) atomicAdd(&la.screen_counts[1], redone);
+            }
+        }
     }
 }
 
@@ -169,13 +366,18 @@ static hipError_t link_one(const LinkArgs& a, int L, int* grid, hipStream_t s) {
         if (!link_shape<R, LOGN>(a, L)) return hipErrorInvalidValue;
         constexpr int FB = link_fb<R, LOGN>();
         constexpr int BLK = OFDM_LINK_BLOCK;
-        CarveSize lds;
-        link_carve<R, LOGN>(lds);
         static_assert(Geo<LOGN, BLK>::SPB * Geo<LOGN, BLK>::TPS == BLK, "whole symbols per workgroup");
-        if (lds.bytes + link_static_lds<R, FB>() > kLdsPerCu) return kLdsOverflow;
         // one workgroup holds a CU: two rounds of the resident workgroups, as the receiver it replaces
-        return rx_go<BLK, Geo<LOGN, BLK>::SPB>(k_link<R, LOGN, FB>, lds.bytes, rx_grid_rounds<R, FB, LOGN>(),
-                                               a.r.c.n_sym, a, grid, s);
+        const auto go = [&](auto screened) {
+            constexpr bool SCREEN = decltype(screened)::value;
+            CarveSize lds;
+            link_carve<R, LOGN, SCREEN, FB>(lds);
+            if (lds.bytes + link_static_lds<R, FB>() > kLdsPerCu) return kLdsOverflow;
+            return rx_go<BLK, Geo<LOGN, BLK>::SPB>(k_link<R, LOGN, FB, SCREEN>, lds.bytes,
+                                                   rx_grid_rounds<R, FB, LOGN>(), a.r.c.n_sym, a, grid, s);
+        };
+        // screen off: the unscreened kernel itself, not the screened one with its decision forced
+        return a.mode == OFDM_LINK_SCREEN_OFF ? go(std::false_type{}) : go(std::true_type{});
     } else {
         return hipErrorInvalidValue;
     }

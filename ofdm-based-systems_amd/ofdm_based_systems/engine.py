@@ -220,6 +220,11 @@ class _Share:
 class LinkEngine:
     plan = None    # the libofdm_hip plan (set by __init__)
     _fused = None  # has_fused, asked of the library once per engine
+    # the fused link's float32 screen (link()): None = ofdm_link (automatic); a B.LINK_SCREEN_* mode =
+    # ofdm_link_screen, counting into screen_counts (device int64 [2], or None).  The counts of a run
+    # do not depend on either.
+    screen_mode = None
+    screen_counts = None
 
     def __init__(self, n_fft: int, cp: int, h_raw: np.ndarray, equalizer: int, luts: Sequence[np.ndarray],
                  sc_lut: Optional[np.ndarray] = None, precision: int = B.OFDM_F64,
@@ -301,10 +306,15 @@ class LinkEngine:
 
     def link(self, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid, counters):
         """ofdm_link: transmit and receive symbols [sym0, sym0 + n_sym) in one kernel, y never leaving
-        the registers; ``stats`` holds the whole stream's record (a power pass, :meth:`tx` with y = None)."""
-        B.check(self._lib.ofdm_link(self.plan.handle, stream, int(seed), B.ptr(stats), int(total_samples),
-                                    float(snr_db), int(noise_on), int(sym0), int(n_sym), int(n_valid),
-                                    B.ptr(counters)))
+        the registers; ``stats`` holds the whole stream's record (a power pass, :meth:`tx` with y = None).
+        With :attr:`screen_mode` set (B.LINK_SCREEN_*), ofdm_link_screen in that mode, adding to
+        :attr:`screen_counts` (device int64 [2]: symbols screened, symbols redone) when that is set."""
+        args = (self.plan.handle, stream, int(seed), B.ptr(stats), int(total_samples), float(snr_db), int(noise_on),
+                int(sym0), int(n_sym), int(n_valid), B.ptr(counters))
+        if self.screen_mode is None:
+            B.check(self._lib.ofdm_link(*args))
+        else:
+            B.check(self._lib.ofdm_link_screen(*args, int(self.screen_mode), B.ptr(self.screen_counts)))
 
     def papr_hist(self, stream, bits_d, seed, sym0, n_sym, edges, hist, sym_out=None, sym_keep=0):
         """ofdm_papr: bin the per-symbol PAPR of symbols [sym0, sym0 + n_sym) at ``edges`` (linear ratios,
