@@ -401,6 +401,45 @@ int ofdm_papr(ofdm_plan_t plan, void* stream, const uint8_t* bits, uint64_t seed
               int64_t sym0, int64_t n_sym, const double* edges, int32_t n_edges,
               uint64_t* hist, double* sym_out, int64_t sym_keep);
 
+/*
+ * The clipped transmitter: ofdm_tx with a soft limiter on the time-domain samples (an entry point added
+ * to ABI 6: nothing of the version's existing interface changes, so the number stands; ofdm_tx itself is
+ * as it was).  For every OFDM symbol take the modulated samples x[0 .. N) -- the IFFT(ortho) output for
+ * OFDM, the mapped points themselves for single carrier -- before the guard is attached and before the
+ * channel.  With a threshold A2 = clip_a2 > 0 on |x|^2:
+ *
+ *     p  = re^2 + im^2                      (in the plan's precision)
+ *     x' = x                   if p <= A2
+ *     x' = x * sqrt(A2 / p)    otherwise    (|x'|^2 = A2: the phase kept, the envelope limited)
+ *
+ * Everything downstream is computed from x': the cyclic prefix (copies of limited samples) or the zero
+ * guard; the FIR across symbol boundaries, the tail a chunk's regenerated predecessor hands on included;
+ * and ofdm_stats (power_sum, x_power_sum, x_peak), so the PAPR they give is that of the stream sent.
+ * The scale factor is not correctly rounded (a reciprocal square root with refinement, ~1 ulp in
+ * complex128, ~2 ulp in complex64); the limiter is continuous and 1-Lipschitz, so the stored samples
+ * stay within the transmitter's own tolerance of the definition.  A sample within rounding of the
+ * threshold may fall on either side of it; both outcomes store the same sample to that tolerance.
+ *
+ * clip_a2: the threshold itself, a double (rounded to float on a complex64 plan); the library never sees
+ *   a level in dB.  Callers derive it as A2 = 10^(clip_db / 10) P_nom, with the nominal mean power of a
+ *   time sample P_nom = (1/N) sum_k mean_i |LUT_l(k)[i]|^2 in double, inactive subcarriers contributing 0,
+ *   k ascending.
+ * clip_counters: optional device uint64 [2], accumulated, not zeroed (NULL: nothing is counted):
+ *   [0] += samples with p > A2, [1] += samples examined -- N per symbol of [sym0, sym0 + n_sym).  The
+ *   guard, inactive symbols past the call's last and a chunk's regenerated predecessor are limited where
+ *   they feed the stream and never counted.  Integers: identical for any batching, grid and rank count.
+ * Every other argument: as ofdm_tx.
+ * OFDM_E_INVALID, before any launch: what ofdm_tx refuses; clip_a2 not finite or <= 0; a plan with an
+ *   order above 256 (the wide map has no limiter built in).  n_sym = 0: an empty call.
+ * Kernels (k_tx, CLIP): the complex128 N = 1024 64-QAM cyclic-prefix OFDM shapes with Philox streams on
+ * the flat and the 8-tap window-FIR throughput transmitters (the flat one, whose symbol leaves the IFFT
+ * multiplied by h0, compares against A2 |h0|^2, the product formed on the host in double: the limiter
+ * commutes with a complex scalar); every other plan, and any plan with caller bits, the generic one.
+ */
+int ofdm_tx_clip(ofdm_plan_t plan, void* stream, const uint8_t* bits, uint64_t seed,
+                 int64_t sym0, int64_t n_sym, void* y, ofdm_stats* stats,
+                 double clip_a2, uint64_t* clip_counters);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,7 @@ struct ofdm_plan_s {
     double gain_mean;
     DevBuf tw, ptw, lut, lut64, h, eq_a, eq_b, axis, sc, active, H64;
     double gtap[3][kWinTaps];  // normalised taps in Gauss form (TxArgs::gtap)
+    double h0_norm2;           // |h0|^2 of the first normalised tap, in double (ofdm_tx_clip: A2 |h0|^2)
     // partial-sum workspaces (3 x kMaxGrid doubles), one per HIP stream the plan has been
     // used on: launches on different streams may run concurrently, and a reduction's
     // partials must not be overwritten by another stream's kernel before k_finalize reads
@@ -424,6 +425,7 @@ int ofdm_plan_create(ofdm_plan_t* out, const ofdm_desc* d, void* stream) {
         std::vector<double> hn(2 * d->n_taps);
         for (int l = 0; l < 2 * d->n_taps; ++l) hn[l] = d->h_raw[l] / sc;
         if ((rc = upload_cpx(p->h, hn, p->prec, s))) return rc;
+        p->h0_norm2 = hn[0] * hn[0] + hn[1] * hn[1];
         for (int l = 0; l < kWinTaps; ++l) {
             const double re = l < d->n_taps ? hn[2 * l] : 0.0, im = l < d->n_taps ? hn[2 * l + 1] : 0.0;
             p->gtap[0][l] = re;
@@ -794,12 +796,29 @@ static void fill_common(ofdm_plan_t p, TxRxCommon& c, const uint8_t* bits, uint6
     }
 }
 
-int ofdm_tx(ofdm_plan_t p, void* stream, const uint8_t* bits, uint64_t seed, int64_t sym0, int64_t n_sym,
-            void* y, ofdm_stats* stats) {
-    if (!p || !p->has_const || p->L < 1) return fail(OFDM_E_INVALID, "ofdm_tx needs a constellation and channel taps");
+// ofdm_tx and ofdm_tx_clip (who; clip: the limiter's threshold and record, or null for ofdm_tx, whose
+// checks, arguments and launch are then what they were)
+struct TxClip {
+    double a2;
+    uint64_t* counters;
+};
+static int tx_call(const char* who, ofdm_plan_t p, void* stream, const uint8_t* bits, uint64_t seed, int64_t sym0,
+                   int64_t n_sym, void* y, ofdm_stats* stats, const TxClip* clip) {
+    if (!p || !p->has_const || p->L < 1)
+        return fail(OFDM_E_INVALID, std::string(who) + " needs a constellation and channel taps");
     if (p->L - 1 > p->n) return fail(OFDM_E_INVALID, "fused path needs channel order <= n_fft");
-    if (n_sym < 0 || sym0 < 0 || !stats) return fail(OFDM_E_INVALID, "bad argument to ofdm_tx");
-    if (int rc = stream_bits_ok(p, bits, "ofdm_tx")) return rc;
+    if (n_sym < 0 || sym0 < 0 || !stats) return fail(OFDM_E_INVALID, std::string("bad argument to ") + who);
+    if (clip) {
+        if (!std::isfinite(clip->a2) || !(clip->a2 > 0.0))
+            return fail(OFDM_E_INVALID, "ofdm_tx_clip: clip_a2 is not a finite positive threshold on |x|^2");
+        if (p->prec == OFDM_F32 && !((float)clip->a2 > 0.f && std::isfinite((float)clip->a2)))
+            return fail(OFDM_E_INVALID, "ofdm_tx_clip: clip_a2 is not a finite positive float on a complex64 plan");
+    }
+    if (int rc = stream_bits_ok(p, bits, who)) return rc;
+    // (after stream_bits_ok: without caller bits a wide plan answers as ofdm_tx does)
+    if (clip && p->wide_plan)
+        return fail(OFDM_E_INVALID, "ofdm_tx_clip: the plan has a constellation above 256 points, and the wide map "
+                                    "has no limiter built in (orders up to 256 only)");
     if (n_sym == 0) return OFDM_OK;
     TxArgs a{};
     // the bits buffer covers global symbols [0, sym0 + n_sym)
@@ -819,13 +838,26 @@ int ofdm_tx(ofdm_plan_t p, void* stream, const uint8_t* bits, uint64_t seed, int
     a.slot = tx_slot(p->logn, p->cp, p->L);
     a.flags = OFDM_ENV_FLAGS("OFDM_ABLATE_TX");
     int grid = 0;  // chosen by the launcher with the kernel (<= kMaxGrid partial records)
-#define CALL(R) launch_tx<R>(p->logn, a, &grid, (hipStream_t)stream)
+#define CALL(R) (clip ? launch_tx_clip<R>(p->logn, a, clip->a2, clip->a2 * p->h0_norm2,                           \
+                                         (unsigned long long*)clip->counters, &grid, (hipStream_t)stream) \
+                      : launch_tx<R>(p->logn, a, &grid, (hipStream_t)stream))
     const hipError_t launch_result = DISPATCH(p, CALL);
 #undef CALL
-    if (launch_result == kLdsOverflow) return lds_overflow(p, "ofdm_tx");
+    if (launch_result == kLdsOverflow) return lds_overflow(p, who);
     HIPCHK(launch_result);
     HIPCHK(launch_finalize_tx(a.partials, grid, (double*)stats, (hipStream_t)stream));
     return OFDM_OK;
+}
+
+int ofdm_tx(ofdm_plan_t p, void* stream, const uint8_t* bits, uint64_t seed, int64_t sym0, int64_t n_sym,
+            void* y, ofdm_stats* stats) {
+    return tx_call("ofdm_tx", p, stream, bits, seed, sym0, n_sym, y, stats, nullptr);
+}
+
+int ofdm_tx_clip(ofdm_plan_t p, void* stream, const uint8_t* bits, uint64_t seed, int64_t sym0, int64_t n_sym,
+                 void* y, ofdm_stats* stats, double clip_a2, uint64_t* clip_counters) {
+    const TxClip clip{clip_a2, clip_counters};
+    return tx_call("ofdm_tx_clip", p, stream, bits, seed, sym0, n_sym, y, stats, &clip);
 }
 
 // The argument path of every fused receiver entry point (who): the plan and the common arguments checked

@@ -624,10 +624,36 @@ constexpr int tx_waves() {
 // REF: the throughput kernel fed the caller's bits (reference streams, ref_lane) -- the same body
 // WIDE: the generic kernel for a plan with an order above 256 (level tables instead of a staged
 // LUT), an instantiation of its own so that the generic kernel of every other plan compiles as before
-template <typename R, int LOGN, int FB, int LT, bool ZPW = false, bool REF = false, bool WIDE = false>
+// CLIP: the soft limiter of ofdm_tx_clip (ofdm_hip.h: the definition) on the symbol in registers,
+// directly after the IFFT: everything downstream -- prefix, FIR, tails, statistics -- sees the limited
+// samples.  Instantiations of their own (ofdm_txclip_inst.hpp).  Invariant: the limiter's arguments are
+// a separate trailing kernel parameter (Tail = TxClipTail) that only CLIP instantiations have; every
+// other k_tx has an empty Tail, i.e. TxArgs alone, so its kernel-argument layout and code stay byte for
+// byte what they were.  tx_tail(tail...) names that one parameter.
+template <typename T>
+__device__ __forceinline__ const T& tx_tail(const T& t) { return t; }
+// The limiter's scale sqrt(A2 / p) for p > A2 > 0 as sa rsqrt(p), sa = sqrt(A2) once per kernel:
+// complex64 v_rsq_f32 (1 ulp); complex128 v_rsq_f64 (~2^-26) and two Newton steps y += y e / 2,
+// e = 1 - p y^2 (relative error ~1e-16 after the first; the second leaves ~1 ulp) -- 9 VALU against
+// the ~45 of an IEEE division followed by an IEEE square root
+template <typename R>
+__device__ __forceinline__ R clip_scale(R sa, R p) {
+    if constexpr (sizeof(R) == 4) {
+        return sa * __builtin_amdgcn_rsqf(p);
+    } else {
+        R y = __builtin_amdgcn_rsq(p);
+        y = __builtin_fma(y * (R)0.5, __builtin_fma(-(p * y), y, (R)1), y);
+        y = __builtin_fma(y * (R)0.5, __builtin_fma(-(p * y), y, (R)1), y);
+        return sa * y;
+    }
+}
+template <typename R, int LOGN, int FB, int LT, bool ZPW = false, bool REF = false, bool WIDE = false,
+          bool CLIP = false, typename... Tail>
 __global__ __launch_bounds__((tx_block<R, FB, LOGN, LT, ZPW>()), (tx_waves<R, FB, LOGN, LT, ZPW>())) void k_tx(
-    TxArgs a) {
+    TxArgs a, Tail... tail) {
+    static_assert(sizeof...(Tail) == (CLIP ? 1 : 0), "CLIP: one trailing TxClipTail; otherwise TxArgs alone");
     static_assert(!WIDE || (FB == 0 && LT == -1 && !REF), "the wide map lives in the generic kernel");
+    static_assert(!CLIP || (!WIDE && !REF && !ZPW), "the limiter: the generic kernel and the Philox throughput forms");
     constexpr int BLK = tx_block<R, FB, LOGN, LT, ZPW>();
     constexpr bool WFIR = FB > 0 && LT > 0;  // register window FIR
     constexpr bool TX_NT = OFDM_TX_NT || (sizeof(R) == 8 && OFDM_TX_NT_F64);  // nontemporal y stores
@@ -768,6 +794,14 @@ __global__ __launch_bounds__((tx_block<R, FB, LOGN, LT, ZPW>()), (tx_waves<R, FB
     // sum |y|^2 in exact fixed point (fx_accum, per lane and symbol); |x|^2 statistics in double
     unsigned long long pq0 = 0, pq1 = 0;
     double px = 0, mx = 0;
+    // CLIP: the threshold on |x|^2 and sqrt of it in the plan's precision; the lane's samples over the
+    // threshold and samples examined, of the call's own symbols (active, c >= 0) only
+    [[maybe_unused]] R clip_a2 = 0, clip_sa = 0;
+    [[maybe_unused]] uint32_t n_clip = 0, n_seen = 0;
+    if constexpr (CLIP) {
+        clip_a2 = (R)tx_tail(tail...).a2;
+        clip_sa = sqrt(clip_a2);
+    }
 
     for (int64_t it = blockIdx.x; it < niter; it += gridDim.x) {
         const int64_t grp = it * G::SPB + ls;
@@ -851,6 +885,29 @@ __global__ __launch_bounds__((tx_block<R, FB, LOGN, LT, ZPW>()), (tx_waves<R, FB
                 }
             }
             if (!(flags & 2) && !scm) fft_sym<R, LOGN, true, FB>(x, row, tw, tt, t);
+            // CLIP: x' = x sqrt(A2 / p) where p = |x|^2 > A2 -- every symbol that feeds the stream, the
+            // regenerated predecessor (c < 0) too; only the call's own symbols are counted.  The
+            // limited samples' |x'|^2, its sum and maximum (in the order of the statistics below,
+            // which take them from here) are formed in the same pass.
+            [[maybe_unused]] R clip_sum = 0, clip_max = 0;
+            if constexpr (CLIP) {
+                uint32_t nc = 0;
+#pragma unroll
+                for (int i = 0; i < E; ++i) {
+                    R p2 = norm2(x[i]);
+                    if (p2 > clip_a2) {
+                        x[i] = cscale(x[i], clip_scale<R>(clip_sa, p2));
+                        p2 = norm2(x[i]);
+                        ++nc;
+                    }
+                    clip_sum += p2;
+                    clip_max = fmax(clip_max, p2);
+                }
+                if (active && c >= 0) {
+                    n_clip += nc;
+                    n_seen += E;
+                }
+            }
             // The prefix repeats samples k >= N - cp.  With cp <= TPS only the lane's last
             // element can be one of them (one loop-invariant compare); otherwise the compares
             // are made per symbol against an opaque copy of N - cp, so they are not hoisted
@@ -870,14 +927,19 @@ __global__ __launch_bounds__((tx_block<R, FB, LOGN, LT, ZPW>()), (tx_waves<R, FB
             R pxs = 0;
             if (active && c >= 0) {
                 R mxs = 0;  // per-symbol partials in the arithmetic precision
+                if constexpr (CLIP) {
+                    pxs = clip_sum;
+                    mxs = clip_max;
+                } else {
 #pragma unroll
-                for (int i = 0; i < E; ++i) {
-                    const R p2 = norm2(x[i]);
-                    pxs += p2;
-                    // (complex128 flat channel: v_max_f64 directly, 15 VALU per symbol and lane fewer;
-                    // the window-FIR kernels schedule fmax without the quieting step already, and the
-                    // complex64 ones grow with it)
-                    mxs = (sizeof(R) == 8 && LT == 0) ? peak_max(mxs, p2) : fmax(mxs, p2);
+                    for (int i = 0; i < E; ++i) {
+                        const R p2 = norm2(x[i]);
+                        pxs += p2;
+                        // (complex128 flat channel: v_max_f64 directly, 15 VALU per symbol and lane fewer;
+                        // the window-FIR kernels schedule fmax without the quieting step already, and the
+                        // complex64 ones grow with it)
+                        mxs = (sizeof(R) == 8 && LT == 0) ? peak_max(mxs, p2) : fmax(mxs, p2);
+                    }
                 }
                 pxs += prefix_sum([&](int i) { return norm2(x[i]); });
                 px += pxs;
@@ -1265,6 +1327,16 @@ __global__ __launch_bounds__((tx_block<R, FB, LOGN, LT, ZPW>()), (tx_waves<R, FB
         pr[1] = pq1;
         a.partials[(size_t)blockIdx.x * kTxFields + 2] = px;
         a.partials[(size_t)blockIdx.x * kTxFields + 3] = mx;
+    }
+    if constexpr (CLIP) {
+        // the record: one 64-bit vector atomic per field and workgroup (integers: any order)
+        const unsigned long long nc = block_sum<unsigned long long, BLK>(n_clip, (unsigned long long*)red);
+        const unsigned long long ns = block_sum<unsigned long long, BLK>(n_seen, (unsigned long long*)red);
+        unsigned long long* rec = tx_tail(tail...).counters;
+        if (threadIdx.x == 0 && rec != nullptr) {
+            if (nc) atomicAdd(&rec[0], nc);
+            if (ns) atomicAdd(&rec[1], ns);
+        }
     }
 }
 

@@ -165,6 +165,15 @@ struct TxArgs {
     const WideAxis* wide;
 };
 
+// ofdm_tx_clip: the limiter's arguments, a second kernel parameter behind TxArgs (k_tx CLIP
+// instantiations only; every other k_tx takes TxArgs alone, as before).  a2 is the threshold on |x|^2
+// the kernel compares against: the flat throughput form, whose symbol leaves the IFFT multiplied by
+// h0, is handed A2 |h0|^2.
+struct TxClipTail {
+    double a2;
+    unsigned long long* counters;  // device uint64[2] (samples clipped, samples examined), accumulated, or null
+};
+
 struct RxArgs {
     TxRxCommon c;
     const void* y;
@@ -272,6 +281,12 @@ hipError_t launch_link(int logn, int L, const LinkArgs& a, int* grid, hipStream_
 // the ABI before it
 template <typename R>
 hipError_t launch_papr(int logn, const PaprArgs& a, int* grid, hipStream_t s);
+
+// the clipped transmitter (ofdm_txclip_inst.hpp); a2: A2, a2_h0: A2 |h0|^2 (the flat throughput form's
+// threshold, computed on the host in double); a wide plan is refused by the ABI before it
+template <typename R>
+hipError_t launch_tx_clip(int logn, const TxArgs& a, double a2, double a2_h0, unsigned long long* counters, int* grid,
+                          hipStream_t s);
 
 hipError_t launch_finalize(const double* partials, int nblocks, int nfields, int max_mask,
                            double* stats, hipStream_t s);

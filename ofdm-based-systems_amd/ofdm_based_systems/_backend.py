@@ -128,6 +128,8 @@ SIGNATURES = {
     # (plan, stream, bits, seed, sym0, n_sym, edges, n_edges, hist, sym_out, sym_keep; edges: a host
     # array of doubles, copied at the call)
     "ofdm_papr": (ctypes.c_int, [_VP, _VP, _VP, _U64, _I64, _I64, _c_f64p, _I32, _VP, _VP, _I64]),
+    # (ofdm_tx_clip joined ABI 6 as an added entry point, as ofdm_papr did)
+    "ofdm_tx_clip": (ctypes.c_int, [_VP, _VP, _VP, _U64, _I64, _I64, _VP, _VP, _F64, _VP]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

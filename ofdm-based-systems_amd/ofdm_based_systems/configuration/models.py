@@ -76,6 +76,8 @@ class SimulationSettings(BaseSettings):
     seed: Optional[int] = Field(None, description="seed for rng_mode='philox'")
     precision: Literal["f64", "f32"] = Field("f64", description="arithmetic precision of the GPU path")
     batch_symbols: Optional[int] = Field(None, description="OFDM symbols per device batch")
+    clip_db: Optional[float] = Field(None, description="soft-limit the transmitted samples' envelope at this level "
+                                     "in dB above the nominal mean sample power (None: a linear transmitter)")
 
     def __str__(self) -> str:
         lines = [

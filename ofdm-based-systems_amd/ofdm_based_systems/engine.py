@@ -37,6 +37,11 @@ with no y in HBM at all and the same results bit for bit.
 SNR sweeps: :meth:`LinkEngine.run_sweep` transmits once and receives at every SNR of a list in one
 pass (ofdm_rx_sweep); point k is ``run(n_sym, snr_k, seed=seed)``.
 
+Clipping: ``LinkEngine(..., clip_db=...)`` limits the envelope of the modulated samples at that level
+above the nominal sample power (ofdm_tx_clip: a soft limiter directly after the IFFT, before the guard
+and the channel); every run of the engine then transmits the limited stream, its statistics describe it,
+and LinkStats carries the count of limited samples (integers, all-reduced behind the error counters).
+
 PAPR distribution: :meth:`LinkEngine.papr` bins the per-symbol PAPR of the stream ``run`` transmits
 (ofdm_papr: the transmitter's map and IFFT, no channel, no receiver) into an integer histogram on the
 device; :class:`PaprStats` carries it and its CCDF.
@@ -106,6 +111,10 @@ class LinkStats:
     received: Optional[np.ndarray] = None
     timings: dict = field(default_factory=dict)
     profile: Optional[SubcarrierProfile] = None  # run(..., profile=True)
+    # an engine with a clip level (LinkEngine(clip_db=...)); None without one
+    clip_db: Optional[float] = None
+    clipped_samples: Optional[int] = None  # samples whose |x|^2 exceeded the threshold
+    clip_samples: Optional[int] = None     # samples examined: N per OFDM symbol
 
 
 def default_papr_edges_db() -> np.ndarray:
@@ -184,6 +193,28 @@ def profile_power(rec: np.ndarray) -> np.ndarray:
     return rec[3].astype(np.float64) * B.FX_HI + rec[2].astype(np.float64) * B.FX_LO
 
 
+def nominal_sample_power(n_fft: int, luts: Sequence[np.ndarray], sc_lut=None) -> float:
+    """P_nom = (1/N) sum_k mean_i |LUT_l(k)[i]|^2 in double, k ascending, inactive subcarriers
+    contributing 0: the nominal mean power of a time sample (include/ofdm_hip.h, ofdm_tx_clip)."""
+    mean = [float(np.mean(np.abs(np.asarray(l, np.complex128)) ** 2)) for l in luts]
+    total = 0.0
+    for k in range(n_fft):
+        l = 0 if sc_lut is None else int(sc_lut[k])
+        total += mean[l] if l >= 0 else 0.0
+    return total / n_fft
+
+
+def clip_threshold(clip_db: float, nominal_power: float) -> float:
+    """A2 = 10^(clip_db / 10) P_nom, the threshold on |x|^2 (finite and positive, or ValueError)."""
+    try:
+        a2 = 10.0 ** (float(clip_db) / 10.0) * nominal_power
+    except OverflowError:
+        a2 = math.inf
+    if not (math.isfinite(a2) and a2 > 0.0):
+        raise ValueError(f"clip_db = {clip_db!r} gives no finite positive threshold (nominal power {nominal_power})")
+    return a2
+
+
 def shard(n: int, rank: int, world: int) -> tuple:
     """Contiguous [lo, hi) share of n items for one rank."""
     lo = (n * rank) // world
@@ -225,13 +256,40 @@ class LinkEngine:
     # do not depend on either.
     screen_mode = None
     screen_counts = None
+    # the soft limiter (ofdm_tx_clip): the level in dB above nominal_power, and the threshold on |x|^2
+    # handed to the library; None = no limiter, ofdm_tx as before
+    clip_db = None
+    clip_a2 = None
+    _nominal = None  # (nominal_sample_power's arguments until first asked for, then its value)
+
+    @property
+    def nominal_power(self) -> Optional[float]:
+        """The nominal mean power of a time sample (:func:`nominal_sample_power`); computed when first
+        asked for -- at construction only on an engine with a clip level."""
+        if isinstance(self._nominal, tuple):
+            self._nominal = nominal_sample_power(*self._nominal)
+        return self._nominal
+
+    @nominal_power.setter
+    def nominal_power(self, value) -> None:
+        self._nominal = value
 
     def __init__(self, n_fft: int, cp: int, h_raw: np.ndarray, equalizer: int, luts: Sequence[np.ndarray],
                  sc_lut: Optional[np.ndarray] = None, precision: int = B.OFDM_F64,
-                 prefix: int = B.PREFIX_CYCLIC, modulator: int = B.MOD_OFDM):
+                 prefix: int = B.PREFIX_CYCLIC, modulator: int = B.MOD_OFDM, clip_db: Optional[float] = None):
         """prefix: cyclic prefix (or none, cp = 0) or zero padding; modulator: OFDM or
         single-carrier OFDM; non-square constellations (PSK) are decided by
-        brute-force nearest point."""
+        brute-force nearest point.
+
+        clip_db: limit the envelope of the modulated samples (after the IFFT, before the guard and
+        the channel) at ``clip_db`` dB above the nominal mean power of a time sample
+        (:func:`nominal_sample_power`); None: a linear transmitter."""
+        self._nominal = (n_fft, list(luts), sc_lut)
+        if clip_db is not None:
+            self.clip_db, self.clip_a2 = float(clip_db), clip_threshold(clip_db, self.nominal_power)
+            if max(len(l) for l in luts) > 256:
+                raise ValueError("clip_db: a constellation above 256 points has no clipped transmitter "
+                                 "(ofdm_tx_clip takes orders up to 256)")
         self.plan = B.Plan(n_fft=n_fft, cp=cp, precision=precision, equalizer=equalizer, luts=list(luts),
                            sc_lut=sc_lut, h_raw=np.asarray(h_raw, np.complex128), prefix=prefix,
                            modulator=modulator)
@@ -281,9 +339,14 @@ class LinkEngine:
         e1.record()
         events.append((name, n_sym, e0, e1))
 
-    def tx(self, stream, bits_d, seed, sym0, n_sym, y, stats):
-        B.check(self._lib.ofdm_tx(self.plan.handle, stream, B.ptr(bits_d), int(seed), int(sym0), int(n_sym),
-                                  B.ptr(y), B.ptr(stats)))
+    def tx(self, stream, bits_d, seed, sym0, n_sym, y, stats, clip_counters=None):
+        """ofdm_tx, or on an engine with a clip level ofdm_tx_clip at its threshold, counting into
+        ``clip_counters`` (device int64 [2], accumulated; None: nothing is counted)."""
+        args = (self.plan.handle, stream, B.ptr(bits_d), int(seed), int(sym0), int(n_sym), B.ptr(y), B.ptr(stats))
+        if self.clip_a2 is None:
+            B.check(self._lib.ofdm_tx(*args))
+        else:
+            B.check(self._lib.ofdm_tx_clip(*args, float(self.clip_a2), B.ptr(clip_counters)))
 
     def rx(self, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits_d, sym0, n_sym,
            n_valid, counters, z_out=None, z_keep=0, profile=None):
@@ -341,6 +404,9 @@ class LinkEngine:
                    all-reduced over the group, as the counters are: every rank holds the whole run's
         events   : if a list, ("ofdm_papr", n_symbols, start, end) HIP events are appended per launch
         """
+        if self.clip_a2 is not None:
+            raise ValueError("papr() on an engine with clip_db: ofdm_papr bins the unclipped stream, and the "
+                             "histogram of a clipped one is not built")
         edb = default_papr_edges_db() if edges_db is None else np.asarray(edges_db, dtype=np.float64).reshape(-1)
         edges = 10.0 ** (edb / 10.0)
         r = self._share(n_sym, group)
@@ -388,11 +454,13 @@ class LinkEngine:
         """The route of a run: ``fused`` None takes the fused one when the plan has a fused form, the
         streams are Philox, there is no received-symbol tap, no profile and every bit is compared;
         False forces the two-kernel path; True raises where no fused form exists."""
-        can = self.has_fused and philox and not tap and not profile and whole
+        clip = self.clip_a2 is not None  # (asked first: a clipped engine never probes the library)
+        can = not clip and self.has_fused and philox and not tap and not profile and whole
         if fused and not can:
             raise ValueError("no fused form for this run: ofdm_link takes a complex128 N = 1024 fixed 64-QAM "
                              "cyclic-prefix OFDM plan over a flat channel without equaliser, Philox streams, "
-                             "no received-symbol tap, no profile and every bit compared")
+                             "no received-symbol tap, no profile and every bit compared, and no clip level "
+                             "(clip_db: the limiter is not built into k_link)")
         return can if fused is None else bool(fused)
 
     def reserve(self, n_sym: int, runs_in_flight: int = 2, group=None, lanes: int = 1) -> None:
@@ -445,7 +513,7 @@ class LinkEngine:
         return done, work
 
     def _schedule(self, r: _Share, seed, bits_d, stats, receive, acc, *, group, y_budget, batch, events,
-                  link=None) -> tuple:
+                  link=None, clip=None) -> tuple:
         """The schedule of run_async and run_sweep_async for this rank's share: the fused route when
         ``link`` is given (run_async decided it, _route_fused) -- the power pass ``tx(y=None)`` over the
         shard, the statistics all-gather, then ``link()``: one ofdm_link over the whole shard, with no y
@@ -455,8 +523,13 @@ class LinkEngine:
         between TX and the first receive the one statistics all-gather, at the end the counters'
         all-reduce (_finish, whose (done, work) are returned).  ``receive(y, sym0, n, resident)``
         enqueues the receiver(s) of symbols [sym0, sym0 + n) held in y; TX is timed into ``events``
-        on the resident path only."""
+        on the resident path only.  ``clip`` (an engine with a clip level: the record, device int64
+        [2] inside ``acc``) goes to the one transmit that covers every symbol once -- the resident
+        one, or the power pass -- and the batch transmits count nothing."""
         stream = r.stream
+        # (tx without a clip level is called as before)
+        count = {} if self.clip_a2 is None else {"clip_counters": clip}
+        quiet = {} if self.clip_a2 is None else {"clip_counters": None}
 
         def reduce_stats():
             # one collective on the TX -> RX critical path: every rank gathers all ranks'
@@ -479,17 +552,18 @@ class LinkEngine:
         per_batch = batch or max(1, min(r.mine, y_budget // self._ybytes()))
         if per_batch >= r.mine:
             y = self._y(r.mine)
-            self._timed(events, "ofdm_tx", r.mine, lambda: self.tx(stream, bits_d, seed, r.lo, r.mine, y, stats))
+            self._timed(events, "ofdm_tx", r.mine,
+                        lambda: self.tx(stream, bits_d, seed, r.lo, r.mine, y, stats, **count))
             reduce_stats()
             receive(y, r.lo, r.mine, True)
         else:
-            self.tx(stream, bits_d, seed, r.lo, r.mine, None, stats)
+            self.tx(stream, bits_d, seed, r.lo, r.mine, None, stats, **count)
             reduce_stats()
             scratch = new_stats(r.dev)
             y = self._y(per_batch)
             for b0 in range(r.lo, r.hi, per_batch):
                 nb = min(per_batch, r.hi - b0)
-                self.tx(stream, bits_d, seed, b0, nb, y, scratch)
+                self.tx(stream, bits_d, seed, b0, nb, y, scratch, **quiet)
                 receive(y, b0, nb, False)
         return self._finish(acc, group, r.dev)
 
@@ -544,10 +618,12 @@ class LinkEngine:
             ni_d = self.upload(np.asarray(normals[1], np.float64))
 
         stats = new_stats(dev)
-        # the counters, and behind them the profile record: one buffer, one all-reduce
-        acc = torch.zeros(2 + (B.PROFILE_ROWS * N if profile else 0), dtype=torch.int64, device=dev)
+        # the counters, and behind them the clip record and the profile record: one buffer, one all-reduce
+        nclip = 0 if self.clip_a2 is None else 2
+        acc = torch.zeros(2 + nclip + (B.PROFILE_ROWS * N if profile else 0), dtype=torch.int64, device=dev)
         counters = acc[:2]
-        prof = acc[2:].view(B.PROFILE_ROWS, N) if profile else None
+        clip = acc[2:4] if nclip else None
+        prof = acc[2 + nclip:].view(B.PROFILE_ROWS, N) if profile else None
         pkw = {"profile": prof} if profile else {}  # (rx without a profile is called as before)
         keep = min(keep_symbols, r.mine)
         z_out = torch.empty((keep, N), dtype=self.cdtype, device=dev) if keep else None
@@ -563,9 +639,9 @@ class LinkEngine:
                 r.stream, seed, stats, r.samples, snr_db, noise_on, r.lo, r.mine, r.n_valid, counters))
 
         done, work = self._schedule(r, seed, bits_d, stats, receive, acc, group=group, y_budget=y_budget,
-                                    batch=batch, events=events, link=link if use_link else None)
+                                    batch=batch, events=events, link=link if use_link else None, clip=clip)
         return PendingLink(n_sym, r.samples, stats, counters, z_out, done, work, prof,
-                           self.bits_per_subcarrier if profile else None)
+                           self.bits_per_subcarrier if profile else None, clip=clip, clip_db=self.clip_db)
 
     # ------------------------------------------------------------------ one-pass SNR sweep
     def run_sweep(self, n_sym: int, snr_dbs, **kw) -> list:
@@ -596,7 +672,11 @@ class LinkEngine:
             raise ValueError("run_sweep needs finite SNR points")
         r = self._share(n_sym, group, n_valid_bits)
         stats = new_stats(r.dev)
-        counters = torch.zeros((len(snrs), 2), dtype=torch.int64, device=r.dev)
+        # the [K][2] counters, and behind them the clip record: one buffer, one all-reduce
+        nclip = 0 if self.clip_a2 is None else 2
+        acc = torch.zeros(2 * len(snrs) + nclip, dtype=torch.int64, device=r.dev)
+        counters = acc[:2 * len(snrs)].view(len(snrs), 2)
+        clip = acc[2 * len(snrs):] if nclip else None
 
         def receive(y, sym0, n, resident):  # (timed per launch on either path)
             for k0 in range(0, len(snrs), B.MAX_SWEEP_POINTS):
@@ -604,9 +684,9 @@ class LinkEngine:
                 self._timed(events, "ofdm_rx_sweep", n, lambda: self.rx_sweep(
                     r.stream, y, seed, stats, r.samples, snrs[k0:k1], sym0, n, r.n_valid, counters[k0:k1]))
 
-        done, work = self._schedule(r, seed, None, stats, receive, counters, group=group, y_budget=y_budget,
-                                    batch=batch, events=events)
-        return PendingSweep(n_sym, r.samples, stats, counters, done, work)
+        done, work = self._schedule(r, seed, None, stats, receive, acc, group=group, y_budget=y_budget,
+                                    batch=batch, events=events, clip=clip)
+        return PendingSweep(n_sym, r.samples, stats, counters, done, work, clip=clip, clip_db=self.clip_db)
 
     def lane_streams(self, lanes: int) -> list:
         """The current stream and lanes - 1 more, kept per engine (their allocator pools persist:
@@ -643,6 +723,9 @@ class LinkEngine:
         fused: as :meth:`run_async`.  On the fused route a run is a power pass and one ofdm_link
         launch, pipelined and laned in the same way (run k+1's power pass before run k's link), with
         no y buffer: ``y_budget`` does not matter."""
+        if self.clip_a2 is not None:
+            raise ValueError("run_pipelined on an engine with clip_db: the pipelined schedule carries no clip "
+                             "record; use run_async or run_sweep")
         seeds = list(seeds)
         snrs = list(snr_db) if isinstance(snr_db, (list, tuple, np.ndarray)) else [snr_db] * len(seeds)
         if len(snrs) != len(seeds):
@@ -718,21 +801,30 @@ class _Pending:
             if self.counters.is_cuda:
                 torch.cuda.current_stream().synchronize()
 
+    clip = None     # the run's clip record (device int64 [2]) on an engine with a clip level
+    clip_db = None
+
     def _statistics(self) -> dict:
-        """LinkStats' fields from the run's statistics record (the same for every SNR point of a sweep)."""
+        """LinkStats' fields from the run's statistics record (the same for every SNR point of a sweep),
+        and with a clip level the clip record's."""
         st = self.stats.cpu().numpy()
         avg = st[1] / self.samples if self.samples else 0.0
         papr = float(10 * np.log10(st[2] / avg)) if avg > 0 else float("inf")
-        return dict(num_ofdm_symbols=self.n_sym, power_sum=float(st[0]), x_power_sum=float(st[1]),
-                    x_peak=float(st[2]), samples=self.samples, papr_db=papr)
+        out = dict(num_ofdm_symbols=self.n_sym, power_sum=float(st[0]), x_power_sum=float(st[1]),
+                   x_peak=float(st[2]), samples=self.samples, papr_db=papr)
+        if self.clip is not None:
+            rec = self.clip.cpu().numpy()
+            out.update(clip_db=self.clip_db, clipped_samples=int(rec[0]), clip_samples=int(rec[1]))
+        return out
 
 
 class PendingLink(_Pending):
     """Device-side results of one :meth:`LinkEngine.run_async` call."""
 
     def __init__(self, n_sym, samples, stats, counters, z_out, done=None, work=None, profile=None,
-                 bits_per_subcarrier=None):
+                 bits_per_subcarrier=None, clip=None, clip_db=None):
         self.n_sym, self.samples = n_sym, samples
+        self.clip, self.clip_db = clip, clip_db
         self.stats, self.counters, self.z_out = stats, counters, z_out
         self.profile, self.bits_per_subcarrier = profile, bits_per_subcarrier
         self.done, self.work = done, work
@@ -757,8 +849,9 @@ class PendingSweep(_Pending):
     """Device-side results of one :meth:`LinkEngine.run_sweep_async` call: the [K][2] counters and
     the run's one statistics record."""
 
-    def __init__(self, n_sym, samples, stats, counters, done=None, work=None):
+    def __init__(self, n_sym, samples, stats, counters, done=None, work=None, clip=None, clip_db=None):
         self.n_sym, self.samples = n_sym, samples
+        self.clip, self.clip_db = clip, clip_db
         self.stats, self.counters = stats, counters
         self.done, self.work = done, work
 

@@ -139,8 +139,16 @@ class Simulation:
         subcarrier_profile: bool = False,
         papr_ccdf: bool = False,
         papr_edges_db=None,
+        clip_db: Optional[float] = None,
     ):
-        """papr_ccdf: also return the distribution of the per-symbol PAPR of the transmitted stream,
+        """clip_db: limit the envelope of the transmitted samples at ``clip_db`` dB above the nominal
+        mean sample power (a soft limiter directly after the IFFT -- for SC-OFDM on the mapped points --
+        before the guard and the channel; ``LinkEngine(clip_db=...)``, ofdm_tx_clip).  Every reported
+        figure then describes the clipped stream, and the result gains ``clip_db``, ``clipped_samples``
+        and ``clipped_fraction``.  Without it the result dict is unchanged.  Needs the fused path and
+        constellation orders up to 256; not combined with ``papr_ccdf``.
+
+        papr_ccdf: also return the distribution of the per-symbol PAPR of the transmitted stream,
         binned on the GPU over every OFDM symbol (engine.PaprStats, ``LinkEngine.papr``): the key
         ``papr_ccdf`` = {``edges_db``, ``ccdf``, ``histogram``, ``num_ofdm_symbols``} as lists, at
         ``papr_edges_db`` (default: -0.125 + 0.25 j dB, j < 64).  Without it the result dict is
@@ -188,6 +196,7 @@ class Simulation:
         self.subcarrier_profile = subcarrier_profile
         self.papr_ccdf = papr_ccdf
         self.papr_edges_db = papr_edges_db
+        self.clip_db = clip_db
 
     def _log(self, message: str) -> None:
         if self.verbose:
@@ -211,7 +220,7 @@ class Simulation:
             except Exception as e:  # noqa: BLE001
                 raise ValueError(f"Failed to load channel model from {path}: {e}")
         extra = {"rng_mode": s.rng_mode, "seed": s.seed, "precision": s.precision,
-                 "batch_symbols": s.batch_symbols}
+                 "batch_symbols": s.batch_symbols, "clip_db": s.clip_db}
         return [
             cls(num_bits=s.num_bits, num_symbols=s.num_symbols, num_subcarriers=s.num_bands,
                 constellation_order=s.constellation_order, constellation_scheme=s.constellation_type,
@@ -324,10 +333,30 @@ class Simulation:
 
         return [s._run(link(k)) for k, s in enumerate(sims)]
 
+    def _check_clip(self, orders=None) -> None:
+        """What a clip level is not combined with, refused before the run: the PAPR histogram (it bins
+        the unclipped stream), user-supplied strategy classes (the composed path has no limiter) and
+        orders above 256 (``orders``: the adaptive loading's, once known)."""
+        if self.papr_ccdf:
+            raise ValueError("papr_ccdf with clip_db: the PAPR histogram of a clipped stream is not built")
+        if (self.MODULATOR_SCHEME_MAPPERS.get(self.modulator_type, OFDMModulator) not in (
+                OFDMModulator, SingleCarrierOFDMModulator)
+                or self.PREFIX_SCHEME_MAPPERS.get(self.prefix_scheme, NoPrefixScheme) not in (
+                    CyclicPrefixScheme, ZeroPaddingPrefixScheme, NoPrefixScheme)
+                or self.CONSTELLATION_SCHEME_MAPPERS.get(self.constellation_scheme, QAMConstellationMapper) not in (
+                    QAMConstellationMapper, PSKConstellationMapper)):
+            raise ValueError("clip_db needs the built-in modulators, prefixes and constellations")
+        top = (self.constellation_order if self.adaptive_modulation_mode == AdaptiveModulationMode.FIXED
+               else 0 if orders is None else int(np.max(orders, initial=0)))
+        if top > 256:
+            raise ValueError(f"clip_db takes constellation orders up to 256, got {top}")
+
     def _run(self, link=None) -> Dict[str, Any]:
         """run(); ``link`` (run_sweep): a callable (make_engine, n_sym, seed, valid_bits) -> LinkStats
         standing in for this simulation's own engine run."""
         results: Dict[str, Any] = {}
+        if self.clip_db is not None:
+            self._check_clip()  # (before anything is launched)
         sp = SerialToParallelConverter()
         noise_model = self.NOISE_SCHEME_MAPPERS.get(self.noise_scheme, AWGNoiseModel)()
         h_raw = np.asarray(DEFAULT_CHANNEL if self.channel_impulse_response is None
@@ -353,6 +382,8 @@ class Simulation:
             orders = np.array([base_mapper.calculate_bit_loading_order(
                 ser=self.desired_symbol_error_rate, snr=p * g / noise_power) for p, g in zip(allocation, gains)],
                 dtype=np.int64)
+            if self.clip_db is not None:
+                self._check_clip(orders)
             mapper: IConstellationMapper = AdaptiveConstellationMapper(orders, base_mapper, N)
             bps = int(np.sum(mapper.get_bits_per_subcarrier()))
             if self.num_symbols is not None:
@@ -443,6 +474,9 @@ class Simulation:
             raise ValueError("subcarrier_profile needs the built-in modulators, prefixes and constellations")
         if not fused and self.papr_ccdf:
             raise ValueError("papr_ccdf needs the built-in modulators, prefixes and constellations")
+        if not fused and self.clip_db is not None:
+            raise ValueError("clip_db needs the fused path (the built-in strategies, channel order and prefix "
+                             "within n_fft)")
         if not fused and link is not None:
             raise ValueError("run_sweep needs the fused path (channel order and prefix within n_fft)")
         t0 = time.perf_counter()
@@ -452,7 +486,8 @@ class Simulation:
             def make_engine():
                 return LinkEngine(N, cp, h_raw, _EQ_KIND[self.equalizator_type], luts, sc, prec,
                                   prefix=B.PREFIX_ZERO if pre_cls is ZeroPaddingPrefixScheme else B.PREFIX_CYCLIC,
-                                  modulator=B.MOD_SC if mod_cls is SingleCarrierOFDMModulator else B.MOD_OFDM)
+                                  modulator=B.MOD_SC if mod_cls is SingleCarrierOFDMModulator else B.MOD_OFDM,
+                                  **({} if self.clip_db is None else {"clip_db": self.clip_db}))
 
             noise_on = isinstance(noise_model, AWGNoiseModel)
             normals = None
@@ -501,6 +536,12 @@ class Simulation:
                 "symbol_errors_per_subcarrier": profile.symbol_errors,
                 "error_power_per_subcarrier": profile.error_power,
                 "mer_db_per_subcarrier": profile.mer_db,
+            })
+        if self.clip_db is not None:
+            results.update({
+                "clip_db": float(self.clip_db),
+                "clipped_samples": st.clipped_samples,
+                "clipped_fraction": st.clipped_samples / st.clip_samples if st.clip_samples else 0.0,
             })
         if self.papr_ccdf:
             results["papr_ccdf"] = {
