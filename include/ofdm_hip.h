@@ -330,21 +330,23 @@ int ofdm_rx_sweep(ofdm_plan_t plan, void* stream, const void* y, uint64_t seed, 
  * compare every bit), returns OFDM_E_INVALID with the reason in ofdm_last_error(), before any launch:
  * there is no fall-back to another path.  n_sym = 0: an empty call.
  * counters: device uint64 [2], accumulated.
- * The float32 screen (ofdm_link_screen below) runs in its automatic mode; the counts are the same in
- * every mode.
+ * The float32 noise screen (ofdm_link_nscreen below) runs in its automatic mode; the counts are the
+ * same in every mode, and with the other screen (ofdm_link_screen).
  */
 int ofdm_link(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
               double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym, int64_t n_valid_bits,
               uint64_t* counters);
 
-/* Modes of the fused link's float32 screen. */
-#define OFDM_LINK_SCREEN_AUTO 0   /* the kernel decides from sigma and the level spacing (ofdm_link) */
+/* Modes of the fused link's float32 screens. */
+#define OFDM_LINK_SCREEN_AUTO 0   /* the kernel decides from sigma and the level spacing */
 #define OFDM_LINK_SCREEN_OFF 1    /* every symbol in complex128: the unscreened kernel (for A/B) */
 #define OFDM_LINK_SCREEN_FORCED 2 /* every symbol screened, whatever the SNR */
 
 /*
- * ofdm_link with the screen's mode and counts (an entry point added to ABI 6: nothing of the version's
- * existing interface changes, so the number stands).  The fused kernel reports integer decisions only,
+ * The fused link with the two-transform float32 screen, its mode and counts (an entry point added to
+ * ABI 6: nothing of the version's existing interface changes, so the number stands).  ofdm_link itself
+ * runs the noise screen (ofdm_link_nscreen below), which is cheaper and decides more symbols; this entry
+ * stays for A/B runs and diagnosis.  The fused kernel reports integer decisions only,
  * and a decision needs complex128 only when the received point lies within rounding distance of a
  * slicer boundary.  A screened wave runs its symbol in float32 first and proves, per element and axis,
  * that the level coordinate is further from every decision boundary than a rigorous bound on the
@@ -361,6 +363,28 @@ int ofdm_link(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_stats* s
 int ofdm_link_screen(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_stats* stats,
                      int64_t total_samples, double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym,
                      int64_t n_valid_bits, uint64_t* counters, int32_t mode, uint64_t* screen_counts);
+
+/*
+ * ofdm_link with the noise screen's mode and counts (an entry point added to ABI 6: nothing of the
+ * version's existing interface changes, so the number stands).  The fused form's channel is one tap
+ * folded into the constellation table and nothing is done to the prefix, so the spectrum the slicer
+ * sees is, in exact arithmetic, N times the table entry of each subcarrier plus the unnormalised FFT of
+ * the symbol's noise.  A screened wave transforms the noise alone in float32 (one transform, where
+ * ofdm_link_screen runs two), adds the table point, and proves per element and axis that the level
+ * coordinate is further from every decision boundary than a rigorous bound on its distance from the
+ * complex128 coordinate -- a bound that scales with the noise, not with the signal; if any element
+ * fails, the wave redoes the whole symbol in complex128.  `counters` receives exactly what ofdm_link's
+ * complex128 arithmetic adds, in every mode and for any share redone.
+ * Automatic mode (what ofdm_link runs) screens when the noise is off or the expected share of
+ * undecided symbols is small enough to pay, a decision made once per launch.
+ * mode: OFDM_LINK_SCREEN_AUTO, _OFF (the unscreened kernel) or _FORCED; anything else is OFDM_E_INVALID.
+ * screen_counts: optional device uint64 [2], accumulated: symbols screened, and symbols of those redone
+ *   in complex128 (both stay as they are when the screen is off).
+ * Everything else -- arguments, refusals, no fall-back -- as ofdm_link.
+ */
+int ofdm_link_nscreen(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_stats* stats,
+                      int64_t total_samples, double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym,
+                      int64_t n_valid_bits, uint64_t* counters, int32_t mode, uint64_t* screen_counts);
 
 /* Edges one ofdm_papr call takes (the kernels hold them, and a bin per edge plus one, in LDS). */
 #define OFDM_MAX_PAPR_EDGES 128

@@ -203,8 +203,9 @@ struct RxSweepArgs {
 };
 
 // ofdm_link: the receiver's arguments (y, nr / ni, z_out, wide and profile unused) and the channel's
-// one tap, which the transmitter folds into its LUT; ofdm_link_screen: the screen's mode
-// (OFDM_LINK_SCREEN_*; ofdm_link: automatic) and its counts
+// one tap, which the transmitter folds into its LUT; ofdm_link_screen, ofdm_link_nscreen: the screen's
+// mode (OFDM_LINK_SCREEN_*; ofdm_link: automatic) and its counts.  Which screen a launch runs is
+// launch_link's noise_screen, not a field: the kernels' arguments stay what they were.
 struct LinkArgs {
     RxArgs r;
     const void* h;
@@ -275,7 +276,7 @@ hipError_t launch_rx_sweep(int logn, const RxSweepArgs& a, int* grid, hipStream_
 // the fused link kernel (ofdm_link_inst.hpp; complex128 only); L: the plan's channel taps.
 // hipErrorInvalidValue: the plan or the arguments have no fused form, nothing was launched
 template <typename R>
-hipError_t launch_link(int logn, int L, const LinkArgs& a, int* grid, hipStream_t s);
+hipError_t launch_link(int logn, int L, const LinkArgs& a, bool noise_screen, int* grid, hipStream_t s);
 
 // the per-symbol PAPR histogram (ofdm_papr_inst.hpp); a plan with an order above 256 is refused by
 // the ABI before it

@@ -14,7 +14,7 @@
 // Shape: complex128, fixed square QAM of FB bits, cyclic-prefix OFDM (or no prefix), flat channel,
 // Philox streams, no equaliser -- bench config (b) at N = 1024, FB = 6.
 //
-// SCREEN (ofdm_link's automatic mode, ofdm_link_screen): the kernel reports integer decisions only, and a
+// SCREEN = kLinkScreenTwo (ofdm_link_screen): the kernel reports integer decisions only, and a
 // decision needs complex128 only when the received point lies within rounding distance of a slicer
 // boundary.  Each wave first runs its symbol in float32 on the complex64 kernels' templates (the float
 // LUT gather, fft_sym<float>, Mwc64x::add_noise, PermSlicer's two packed FMAs) and proves, per element
@@ -24,6 +24,15 @@
 // popcount is the symbol's count (the levels are the float64 path's, so the words are); otherwise the
 // wave re-seeds and redoes the whole symbol on the complex128 statements, unchanged.  The counts are
 // the unscreened kernel's whatever share is redone.
+//
+// SCREEN = kLinkScreenNoise (ofdm_link's automatic mode, ofdm_link_nscreen): the channel is one tap folded
+// into the LUT and nothing is done to the prefix, so in exact arithmetic the spectrum the slicer sees is
+// z_k = N l_k + G_k, l the folded LUT entry of subcarrier k and G the unnormalised FFT of the symbol's
+// noise: the IFFT and the FFT of its output only reproduce N l_k, a number already in LDS.  The noise
+// screen transforms the noise alone in float32 (one transform, forward twiddles only) and adds the LUT
+// point scaled by N (exact: N is a power of two) per element -- element i of a lane is subcarrier byte i
+// of the lane block on the way in and on the way out.  Its bound scales with the noise, not the signal
+// (nscreen_const below); the ballot, the counts and the redo are the same.
 #pragma once
 
 #include "ofdm_kernels_inst.hpp"
@@ -41,17 +50,21 @@ namespace ofdm {
 #define OFDM_LINK_WAVES 3
 #endif
 
+// k_link's SCREEN: none, the two-transform float32 screen, the noise screen
+constexpr int kLinkScreenNone = 0, kLinkScreenTwo = 1, kLinkScreenNoise = 2;
+
 template <typename R>
 struct LinkLds {
     cpx<R>* tt;  // per-pass twiddles [forward | inverse]
     AxisInfo* axis;
     unsigned char* rowmem;
     unsigned long long* redc;
-    // SCREEN: the same twiddles [forward | inverse] and the folded LUT rounded to float32
+    // kLinkScreenTwo: the same twiddles [forward | inverse] and the folded LUT rounded to float32;
+    // kLinkScreenNoise: the forward twiddles only, and that LUT times N
     cpx<float>* tt32;
     cpx<float>* lut32;
 };
-template <typename R, int LOGN, bool SCREEN = false, int FB = 0, typename CV>
+template <typename R, int LOGN, int SCREEN = kLinkScreenNone, int FB = 0, typename CV>
 __host__ __device__ __forceinline__ constexpr LinkLds<R> link_carve(CV& cv) {
     using G = Geo<LOGN, OFDM_LINK_BLOCK>;
     LinkLds<R> m{};
@@ -60,7 +73,7 @@ __host__ __device__ __forceinline__ constexpr LinkLds<R> link_carve(CV& cv) {
     m.rowmem = cv.template take<unsigned char>((size_t)G::SPB * G::PADN * sizeof(R));
     m.redc = cv.template take<unsigned long long>(OFDM_LINK_BLOCK / 64);
     m.tt = cv.template take<cpx<R>>(2 * tt_size(LOGN));
-    m.tt32 = cv.template take<cpx<float>>(SCREEN ? 2 * tt_size(LOGN) : 0);
+    m.tt32 = cv.template take<cpx<float>>(SCREEN == kLinkScreenTwo ? 2 * tt_size(LOGN) : SCREEN ? tt_size(LOGN) : 0);
     m.lut32 = cv.template take<cpx<float>>(SCREEN ? (1 << FB) : 0);
     return m;
 }
@@ -154,7 +167,43 @@ __host__ __device__ inline ScreenConst screen_const(double lvl, double amax, dou
     return c;
 }
 
-template <typename R, int LOGN, int FB, bool SCREEN = false>
+// ---- the noise screen's bound
+// zhat_k = fl(N l32_k + ghat_k), ghat the float32 transform of nhat = fl(r e), the once-rounded float32
+// product the complex128 kernel takes exactly.  ||nhat - n||_2 <= u ||n||_2, so by the theorem above and
+// linearity ||ghat - G||_2 <= (66.6 + 1) u ||G||_2 (1 + O(u)); the LUT's rounding is u N a, the final
+// add's u (N a + |ghat_k|), the complex128 kernel's own two transforms 70 2^-53 (2 N^1.5 a + ||G||_2),
+// below 1e-3 u N a.  With |ghat_k| <= ||ghat||_2 and ||G||_2 <= ||ghat||_2 (1 + 68 u):
+//   |zhat_k - z64_k| <= kNScreenK u ||ghat||_2 + kNScreenC u N a,  kNScreenK = 72, kNScreenC = 3;
+// 72 over 68.6 and 3 over 2 cover the 1 / (1 - t eta), the second-order terms, the float64 side and the
+// float32 evaluation of the norm and of this bound.
+constexpr double kNScreenK = 72.0;
+constexpr double kNScreenC = 3.0;
+// automatic mode: a screened symbol costs about half a complex128 one, so the screen pays up to about
+// half of the symbols redone.  Measured (profiles/link_nscreen_ab.txt): forced wins down to 8 dB (0.46
+// redone, lambda below 0.487) and loses from 6 dB (0.53 redone, lambda 0.513); lambda counts the two levels
+// beside a boundary only and so saturates at low SNR, where the shares redone keep growing
+constexpr double kNScreenMaxUndecided = 0.5;
+
+// delta in levels = cz ||ghat||_2 + c0, and the expected undecided axes per symbol (||ghat||_2 ~ N sigma sqrt 2)
+template <int LOGN, int FB>
+__host__ __device__ inline ScreenConst nscreen_const(double lvl, double amax, double sigma) {
+    constexpr double N = (double)(1 << LOGN), side = (double)(1 << (FB / 2));
+    const double kz = kNScreenK * kScreenU * lvl;
+    const double k0 = kNScreenC * kScreenU * lvl * N * amax + kScreenSlicerU * kScreenU;
+    ScreenConst c;
+    c.cz = (float)(1.001 * kz);
+    c.c0 = (float)(1.001 * k0);
+    c.undecided = 0.0;
+    if (sigma > 0.0) {
+        const double sc = sigma * sqrt(N) * lvl;
+        const double delta = kz * N * sigma * 1.4142135623730951 + k0;
+        const double phi = exp(-0.125 / (sc * sc)) * 0.3989422804014327 / sc;
+        c.undecided = 2.0 * N * (side - 1.0) * (2.0 / side) * 2.0 * delta * phi;
+    }
+    return c;
+}
+
+template <typename R, int LOGN, int FB, int SCREEN = kLinkScreenNone>
 __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkArgs la) {
     static_assert(sizeof(R) == 8 && FB > 1 && !(FB & 1), "complex128 fixed square QAM");
     static_assert(uses_tt<R, LOGN, FB>() && Geo<LOGN>::TPS >= 64, "a symbol per wave, per-pass twiddles in LDS");
@@ -215,7 +264,7 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
     [[maybe_unused]] ScreenSlicer<FB> fslicer;
     [[maybe_unused]] bool screen = false;
     [[maybe_unused]] float cz = 0, c0 = 0;
-    if constexpr (SCREEN) {
+    if constexpr (SCREEN == kLinkScreenTwo) {
         for (int i = threadIdx.x; i < 2 * TTS; i += BLK) tt32[i] = mk<float>((float)tt[i].re, (float)tt[i].im);
         double amax = 0;
         for (int i = 0; i < (1 << FB); ++i) {
@@ -230,6 +279,24 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
         cz = sc.cz;
         c0 = sc.c0;
         screen = la.mode == OFDM_LINK_SCREEN_FORCED || !noise || sc.undecided < kScreenMaxUndecided;
+        __syncthreads();
+    }
+    if constexpr (SCREEN == kLinkScreenNoise) {
+        // the forward twiddles only, and the float32 LUT times N (a power of two: the same rounding)
+        for (int i = threadIdx.x; i < TTS; i += BLK) tt32[i] = mk<float>((float)tt[i].re, (float)tt[i].im);
+        double amax = 0;
+        for (int i = 0; i < (1 << FB); ++i) {
+            const C v = lut_s[i];
+            amax = fmax(amax, v.re * v.re + v.im * v.im);
+            if (i == (int)threadIdx.x) lut32[i] = mk<float>((float)(1 << LOGN) * (float)v.re, (float)(1 << LOGN) * (float)v.im);
+        }
+        static_assert((1 << FB) <= BLK, "one LUT entry per thread");
+        fslicer.load(axis[0], cm.scale);
+        const ScreenConst sc = nscreen_const<LOGN, FB>((double)fslicer.mul.x * (double)(PermSlicer<FB>::SIDE - 1),
+                                                       sqrt(amax), sigma_d);
+        cz = sc.cz;
+        c0 = sc.c0;
+        screen = la.mode == OFDM_LINK_SCREEN_FORCED || !noise || sc.undecided < kNScreenMaxUndecided;
         __syncthreads();
     }
 
@@ -250,18 +317,33 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
                     TxBits<FB, TPS> tb;
                     tb.load(cm, sg, t, nullptr, true);
                     CF xf[E];
-                    static_for<0, E>([&](auto I) { xf[I] = lut32[tb.template fixed<I>()]; });
-                    fft_sym<float, LOGN, true, FB>(xf, rowf, tt32, tt32 + TTS, t);
-                    sym_sync<TPS>();  // the IFFT's last pass has read the row
-                    if (noise) {
-#pragma unroll
-                        for (int i = 0; i < E; ++i) tb.g.add_noise(xf[i].v, ntab, i);
-                    }
-                    fft_sym<float, LOGN, false, FB>(xf, rowf, tt32, tt32, t);
-                    // delta of this symbol, in levels, from its own norm
                     f32x2 acc = f32x2{0.f, 0.f};
+                    if constexpr (SCREEN == kLinkScreenTwo) {
+                        static_for<0, E>([&](auto I) { xf[I] = lut32[tb.template fixed<I>()]; });
+                        fft_sym<float, LOGN, true, FB>(xf, rowf, tt32, tt32 + TTS, t);
+                        sym_sync<TPS>();  // the IFFT's last pass has read the row
+                        if (noise) {
 #pragma unroll
-                    for (int i = 0; i < E; ++i) acc = __builtin_elementwise_fma(xf[i].v, xf[i].v, acc);
+                            for (int i = 0; i < E; ++i) tb.g.add_noise(xf[i].v, ntab, i);
+                        }
+                        fft_sym<float, LOGN, false, FB>(xf, rowf, tt32, tt32, t);
+                        // delta of this symbol, in levels, from its own norm
+#pragma unroll
+                        for (int i = 0; i < E; ++i) acc = __builtin_elementwise_fma(xf[i].v, xf[i].v, acc);
+                    } else {
+                        // the noise alone (each sample the once-rounded float32 product), its transform
+                        // and that transform's norm; then the point N l32 of each element's subcarrier
+#pragma unroll
+                        for (int i = 0; i < E; ++i) xf[i] = mk<float>(0.f, 0.f);
+                        if (noise) {
+#pragma unroll
+                            for (int i = 0; i < E; ++i) tb.g.add_noise(xf[i].v, ntab, i);
+                            fft_sym<float, LOGN, false, FB>(xf, rowf, tt32, tt32, t);
+#pragma unroll
+                            for (int i = 0; i < E; ++i) acc = __builtin_elementwise_fma(xf[i].v, xf[i].v, acc);
+                        }
+                        static_for<0, E>([&](auto I) { xf[I].v += lut32[tb.template fixed<I>()].v; });
+                    }
                     float n2 = acc.x + acc.y;
 #pragma unroll
                     for (int off = 32; off > 0; off >>= 1) n2 += __shfl_xor(n2, off, 64);
@@ -361,7 +443,7 @@ static bool link_shape(const LinkArgs& a, int L) {
 }
 
 template <typename R, int LOGN>
-static hipError_t link_one(const LinkArgs& a, int L, int* grid, hipStream_t s) {
+static hipError_t link_one(const LinkArgs& a, int L, bool noise_screen, int* grid, hipStream_t s) {
     if constexpr (link_fb<R, LOGN>() > 0) {
         if (!link_shape<R, LOGN>(a, L)) return hipErrorInvalidValue;
         constexpr int FB = link_fb<R, LOGN>();
@@ -369,7 +451,7 @@ static hipError_t link_one(const LinkArgs& a, int L, int* grid, hipStream_t s) {
         static_assert(Geo<LOGN, BLK>::SPB * Geo<LOGN, BLK>::TPS == BLK, "whole symbols per workgroup");
         // one workgroup holds a CU: two rounds of the resident workgroups, as the receiver it replaces
         const auto go = [&](auto screened) {
-            constexpr bool SCREEN = decltype(screened)::value;
+            constexpr int SCREEN = decltype(screened)::value;
             CarveSize lds;
             link_carve<R, LOGN, SCREEN, FB>(lds);
             if (lds.bytes + link_static_lds<R, FB>() > kLdsPerCu) return kLdsOverflow;
@@ -377,7 +459,9 @@ static hipError_t link_one(const LinkArgs& a, int L, int* grid, hipStream_t s) {
                                                    rx_grid_rounds<R, FB, LOGN>(), a.r.c.n_sym, a, grid, s);
         };
         // screen off: the unscreened kernel itself, not the screened one with its decision forced
-        return a.mode == OFDM_LINK_SCREEN_OFF ? go(std::false_type{}) : go(std::true_type{});
+        if (a.mode == OFDM_LINK_SCREEN_OFF) return go(std::integral_constant<int, kLinkScreenNone>{});
+        return noise_screen ? go(std::integral_constant<int, kLinkScreenNoise>{})
+                            : go(std::integral_constant<int, kLinkScreenTwo>{});
     } else {
         return hipErrorInvalidValue;
     }
@@ -385,10 +469,10 @@ static hipError_t link_one(const LinkArgs& a, int L, int* grid, hipStream_t s) {
 
 // hipErrorInvalidValue: no fused form for this plan or these arguments (nothing launched)
 template <typename R>
-hipError_t launch_link(int logn, int L, const LinkArgs& a, int* grid, hipStream_t s) {
+hipError_t launch_link(int logn, int L, const LinkArgs& a, bool noise_screen, int* grid, hipStream_t s) {
 #define OFDM_LINK_CASE(LG) \
     case LG:               \
-        return link_one<R, LG>(a, L, grid, s);
+        return link_one<R, LG>(a, L, noise_screen, grid, s);
     switch (logn) {
         OFDM_LOGN_CASES(OFDM_LINK_CASE)
         default:
