@@ -330,8 +330,9 @@ int ofdm_rx_sweep(ofdm_plan_t plan, void* stream, const void* y, uint64_t seed, 
  * compare every bit), returns OFDM_E_INVALID with the reason in ofdm_last_error(), before any launch:
  * there is no fall-back to another path.  n_sym = 0: an empty call.
  * counters: device uint64 [2], accumulated.
- * The float32 noise screen (ofdm_link_nscreen below) runs in its automatic mode; the counts are the
- * same in every mode, and with the other screen (ofdm_link_screen).
+ * The float32 noise screen with the sparse slicer (ofdm_link_sparse below) runs in its automatic mode;
+ * the counts are the same in every mode, and with the other screens (ofdm_link_nscreen,
+ * ofdm_link_screen).
  */
 int ofdm_link(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
               double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym, int64_t n_valid_bits,
@@ -365,8 +366,10 @@ int ofdm_link_screen(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_s
                      int64_t n_valid_bits, uint64_t* counters, int32_t mode, uint64_t* screen_counts);
 
 /*
- * ofdm_link with the noise screen's mode and counts (an entry point added to ABI 6: nothing of the
- * version's existing interface changes, so the number stands).  The fused form's channel is one tap
+ * The fused link with the noise screen, every quad sliced, its mode and counts (an entry point added to
+ * ABI 6: nothing of the version's existing interface changes, so the number stands).  ofdm_link itself
+ * runs this screen with the sparse slicer (ofdm_link_sparse below); this entry stays as its A/B
+ * baseline.  The fused form's channel is one tap
  * folded into the constellation table and nothing is done to the prefix, so the spectrum the slicer
  * sees is, in exact arithmetic, N times the table entry of each subcarrier plus the unnormalised FFT of
  * the symbol's noise.  A screened wave transforms the noise alone in float32 (one transform, where
@@ -375,8 +378,8 @@ int ofdm_link_screen(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_s
  * complex128 coordinate -- a bound that scales with the noise, not with the signal; if any element
  * fails, the wave redoes the whole symbol in complex128.  `counters` receives exactly what ofdm_link's
  * complex128 arithmetic adds, in every mode and for any share redone.
- * Automatic mode (what ofdm_link runs) screens when the noise is off or the expected share of
- * undecided symbols is small enough to pay, a decision made once per launch.
+ * Automatic mode screens when the noise is off or the expected share of undecided symbols is small
+ * enough to pay, a decision made once per launch (ofdm_link's rule for screening).
  * mode: OFDM_LINK_SCREEN_AUTO, _OFF (the unscreened kernel) or _FORCED; anything else is OFDM_E_INVALID.
  * screen_counts: optional device uint64 [2], accumulated: symbols screened, and symbols of those redone
  *   in complex128 (both stay as they are when the screen is off).
@@ -385,6 +388,30 @@ int ofdm_link_screen(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_s
 int ofdm_link_nscreen(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_stats* stats,
                       int64_t total_samples, double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym,
                       int64_t n_valid_bits, uint64_t* counters, int32_t mode, uint64_t* screen_counts);
+
+/*
+ * ofdm_link with the sparse slicer's mode and counts (an entry point added to ABI 6: nothing of the
+ * version's existing interface changes, so the number stands).  The kernel is the noise screen
+ * (ofdm_link_nscreen above) up to the symbol's bound.  Before the table point is added, a screened wave
+ * holds the float32 transform of the noise alone, and for each quad -- elements 4q .. 4q+3 of every lane,
+ * 512 components of the wave -- it takes the largest modulus of a component and compares it with a
+ * per-symbol threshold T.  T is chosen so that a quad with no component over it provably gives the
+ * transmitted levels and a margin inside the screen's: the add, the slicer and the counts are skipped
+ * for it, and run unchanged for every other quad.  The counters, the set of symbols redone in complex128
+ * and the screen's two counts are ofdm_link_nscreen's for every input.
+ * Automatic mode (what ofdm_link runs) decides once per launch, from sigma and the level spacing, both
+ * whether to screen (the noise screen's rule) and whether to test the quads or slice them all (when
+ * the expected number of components over T per quad is too large for the test to pay).
+ * mode: OFDM_LINK_SCREEN_AUTO; _OFF (the noise screen itself in its automatic mode, sparse_counts left
+ *   as they are); _FORCED (every symbol screened and every quad tested, whatever the SNR); anything else
+ *   is OFDM_E_INVALID.
+ * sparse_counts: optional device uint64 [4], accumulated: symbols screened, symbols of those redone in
+ *   complex128, quads tested, and quads of those sliced (a launch that slices every quad tests none).
+ * Everything else -- arguments, refusals, no fall-back -- as ofdm_link.
+ */
+int ofdm_link_sparse(ofdm_plan_t plan, void* stream, uint64_t seed, const ofdm_stats* stats,
+                     int64_t total_samples, double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym,
+                     int64_t n_valid_bits, uint64_t* counters, int32_t mode, uint64_t* sparse_counts);
 
 /* Edges one ofdm_papr call takes (the kernels hold them, and a bin per edge plus one, in LDS). */
 #define OFDM_MAX_PAPR_EDGES 128

@@ -965,8 +965,9 @@ int ofdm_rx_sweep(ofdm_plan_t p, void* stream, const void* y, uint64_t seed, con
     return OFDM_OK;
 }
 
-// ofdm_link, ofdm_link_nscreen (noise_screen) and ofdm_link_screen (mode, screen_counts: the screen's)
-static int link_call(bool noise_screen, ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
+// ofdm_link, ofdm_link_sparse, ofdm_link_nscreen and ofdm_link_screen (screen: the kernel's, kLinkScreen*;
+// mode, screen_counts: the screen's)
+static int link_call(int screen, ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
                      double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym, int64_t n_valid_bits,
                      uint64_t* counters, int32_t mode, uint64_t* screen_counts) {
     // what has a fused form, each refusal naming its reason (the launcher's link_shape holds the same
@@ -996,11 +997,12 @@ static int link_call(bool noise_screen, ofdm_plan_t p, void* stream, uint64_t se
     if (!run) return rc;
     a.r.y = nullptr;
     a.r.snr_lin = std::pow(10.0, snr_db / 10.0);
+    a.r.flags = OFDM_ENV_FLAGS("OFDM_ABLATE_RX");  // (8: the noise screen without its add and slicer; ablation builds)
     a.h = p->h.p;
     a.mode = mode;
     a.screen_counts = (unsigned long long*)screen_counts;
     int grid = 0;
-    const hipError_t launch_result = launch_link<double>(p->logn, p->L, a, noise_screen, &grid, (hipStream_t)stream);
+    const hipError_t launch_result = launch_link<double>(p->logn, p->L, a, screen, &grid, (hipStream_t)stream);
     if (launch_result == hipErrorInvalidValue) return fail(OFDM_E_INVALID, "ofdm_link: no fused form for this plan");
     if (launch_result == kLdsOverflow) return lds_overflow(p, "ofdm_link");
     HIPCHK(launch_result);
@@ -1010,8 +1012,21 @@ static int link_call(bool noise_screen, ofdm_plan_t p, void* stream, uint64_t se
 int ofdm_link(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
               double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym, int64_t n_valid_bits,
               uint64_t* counters) {
-    return link_call(true, p, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits, counters,
-                     OFDM_LINK_SCREEN_AUTO, nullptr);
+    return link_call(kLinkScreenSparse, p, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits,
+                     counters, OFDM_LINK_SCREEN_AUTO, nullptr);
+}
+
+int ofdm_link_sparse(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
+                     double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym, int64_t n_valid_bits,
+                     uint64_t* counters, int32_t mode, uint64_t* sparse_counts) {
+    if (mode != OFDM_LINK_SCREEN_AUTO && mode != OFDM_LINK_SCREEN_OFF && mode != OFDM_LINK_SCREEN_FORCED)
+        return fail(OFDM_E_INVALID, "ofdm_link_sparse: mode " + std::to_string(mode) + " is not an OFDM_LINK_SCREEN_* value");
+    // off: the noise screen itself in its automatic mode, and nothing counted
+    if (mode == OFDM_LINK_SCREEN_OFF)
+        return link_call(kLinkScreenNoise, p, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits,
+                         counters, OFDM_LINK_SCREEN_AUTO, nullptr);
+    return link_call(kLinkScreenSparse, p, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits,
+                     counters, mode, sparse_counts);
 }
 
 int ofdm_link_nscreen(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
@@ -1019,8 +1034,8 @@ int ofdm_link_nscreen(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_sta
                       uint64_t* counters, int32_t mode, uint64_t* screen_counts) {
     if (mode != OFDM_LINK_SCREEN_AUTO && mode != OFDM_LINK_SCREEN_OFF && mode != OFDM_LINK_SCREEN_FORCED)
         return fail(OFDM_E_INVALID, "ofdm_link_nscreen: mode " + std::to_string(mode) + " is not an OFDM_LINK_SCREEN_* value");
-    return link_call(true, p, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits, counters,
-                     mode, screen_counts);
+    return link_call(kLinkScreenNoise, p, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits,
+                     counters, mode, screen_counts);
 }
 
 int ofdm_link_screen(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
@@ -1028,8 +1043,8 @@ int ofdm_link_screen(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stat
                      uint64_t* counters, int32_t mode, uint64_t* screen_counts) {
     if (mode != OFDM_LINK_SCREEN_AUTO && mode != OFDM_LINK_SCREEN_OFF && mode != OFDM_LINK_SCREEN_FORCED)
         return fail(OFDM_E_INVALID, "ofdm_link_screen: mode " + std::to_string(mode) + " is not an OFDM_LINK_SCREEN_* value");
-    return link_call(false, p, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits, counters,
-                     mode, screen_counts);
+    return link_call(kLinkScreenTwo, p, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits,
+                     counters, mode, screen_counts);
 }
 
 int ofdm_papr(ofdm_plan_t p, void* stream, const uint8_t* bits, uint64_t seed, int64_t sym0, int64_t n_sym,

@@ -205,13 +205,18 @@ struct RxSweepArgs {
 // ofdm_link: the receiver's arguments (y, nr / ni, z_out, wide and profile unused) and the channel's
 // one tap, which the transmitter folds into its LUT; ofdm_link_screen, ofdm_link_nscreen: the screen's
 // mode (OFDM_LINK_SCREEN_*; ofdm_link: automatic) and its counts.  Which screen a launch runs is
-// launch_link's noise_screen, not a field: the kernels' arguments stay what they were.
+// launch_link's `screen`, not a field: the kernels' arguments stay what they were.
 struct LinkArgs {
     RxArgs r;
     const void* h;
     int mode;
-    unsigned long long* screen_counts;  // device uint64[2] (symbols screened, symbols redone), accumulated, or null
+    // device uint64[2] (symbols screened, symbols redone), accumulated, or null; kLinkScreenSparse:
+    // uint64[4], quads tested and quads sliced behind them
+    unsigned long long* screen_counts;
 };
+// k_link's SCREEN and launch_link's `screen`: none, the two-transform float32 screen, the noise screen,
+// the noise screen slicing only the quads its noise can reach (ofdm_link_inst.hpp)
+constexpr int kLinkScreenNone = 0, kLinkScreenTwo = 1, kLinkScreenNoise = 2, kLinkScreenSparse = 3;
 
 // ofdm_papr: the transmitter's common arguments (no channel, no statistics), the histogram, the optional
 // per-symbol trace and the edges (linear ratios, strictly increasing)
@@ -276,7 +281,7 @@ hipError_t launch_rx_sweep(int logn, const RxSweepArgs& a, int* grid, hipStream_
 // the fused link kernel (ofdm_link_inst.hpp; complex128 only); L: the plan's channel taps.
 // hipErrorInvalidValue: the plan or the arguments have no fused form, nothing was launched
 template <typename R>
-hipError_t launch_link(int logn, int L, const LinkArgs& a, bool noise_screen, int* grid, hipStream_t s);
+hipError_t launch_link(int logn, int L, const LinkArgs& a, int screen, int* grid, hipStream_t s);
 
 // the per-symbol PAPR histogram (ofdm_papr_inst.hpp); a plan with an order above 256 is refused by
 // the ABI before it

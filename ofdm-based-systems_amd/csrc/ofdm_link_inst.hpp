@@ -33,6 +33,15 @@
 // point scaled by N (exact: N is a power of two) per element -- element i of a lane is subcarrier byte i
 // of the lane block on the way in and on the way out.  Its bound scales with the noise, not the signal
 // (nscreen_const below); the ballot, the counts and the redo are the same.
+//
+// SCREEN = kLinkScreenSparse (ofdm_link's automatic mode, ofdm_link_sparse): the noise screen, slicing only
+// the quads the noise can reach.  Before the point is added xf holds the bare ghat, and a quad (elements
+// 4q .. 4q+3 of every lane) none of whose 512 components exceeds T in modulus provably gives the
+// transmitted levels and a margin inside thr (sparse_eps below): its difference word
+// is 0 and it leaves m <= thr, so the add, diff_margin and the counts are skipped for it -- one max3
+// chain and a ballot per quad.  The counts, the symbols redone and the screen's counts are the noise
+// screen's for every input.  Whether a launch tests its quads or runs the noise screen's unrolled
+// sequence is a workgroup-uniform decision beside `screen` (sparse_mu below).
 #pragma once
 
 #include "ofdm_kernels_inst.hpp"
@@ -50,8 +59,7 @@ namespace ofdm {
 #define OFDM_LINK_WAVES 3
 #endif
 
-// k_link's SCREEN: none, the two-transform float32 screen, the noise screen
-constexpr int kLinkScreenNone = 0, kLinkScreenTwo = 1, kLinkScreenNoise = 2;
+// (k_link's SCREEN -- kLinkScreenNone, Two, Noise, Sparse -- is ofdm_launch.hpp's: the ABI names one)
 
 template <typename R>
 struct LinkLds {
@@ -60,7 +68,7 @@ struct LinkLds {
     unsigned char* rowmem;
     unsigned long long* redc;
     // kLinkScreenTwo: the same twiddles [forward | inverse] and the folded LUT rounded to float32;
-    // kLinkScreenNoise: the forward twiddles only, and that LUT times N
+    // kLinkScreenNoise, kLinkScreenSparse: the forward twiddles only, and that LUT times N
     cpx<float>* tt32;
     cpx<float>* lut32;
 };
@@ -203,11 +211,52 @@ __host__ __device__ inline ScreenConst nscreen_const(double lvl, double amax, do
     return c;
 }
 
+// ---- the sparse slicer's threshold
+// A skipped quad must be one for which diff_margin returns 0 and leaves m <= thr.  In levels, with k the
+// table point's own level on an axis, rho = |p lvl + off - k| the point's own distance from it under the
+// slicer's float32 constants (taken from the table in the prologue, so neither constant's rounding needs a
+// bound), c = ghat lvl and S the side: the final add moves the coordinate by at most u S / 2, the first
+// FMA by u (S - 1/2), the clamp moves it towards [0, S - 1], which holds k, the magic sum rounds the exact
+// product v (S - 1) to the nearest integer (so the level is k while the distance is below 1/2), the
+// margin's FMA adds u / 2, thr = fl(1/2 - delta) is off by u / 4 and T = fl(fl(thr - e0) fl(1 / lvl)) by
+// 1.25 u of a level: (1.5 S + 1.5) u in all.  eps = (1.5 S + 6) u leaves 4.5 u for the second-order terms
+// and the double evaluation of rho; e0 = 1.001 (eps + rho) covers its own rounding to float32.
+//   |ghat component| <= T = (thr - e0) / lvl for all eight of a quad in every lane  =>  d = 0, m_quad <= thr.
+constexpr double sparse_eps(int side) { return (1.5 * side + 6.0) * kScreenU; }
+// automatic mode: test the quads when the expected number of components over T per quad index and wave
+// is below this (a share 1 - exp(-mu) of the quads sliced).  Measured (profiles/link_sparse_ab.txt): the
+// forced test wins down to 23 dB (mu = 1.05, 0.65 of the quads sliced: 1.654 against 1.706 ms) and loses
+// from 22 dB (mu = 3.1, 0.95 sliced: 1.811 against 1.729) -- a sliced quad pays its test and the branch
+constexpr double kSparseMaxPerQuad = 2.0;
+// mu = 8 * 64 * 2 Q(T_levels / sigma_c): sigma_c the noise's deviation per component in levels, T_levels at
+// the expected norm ||ghat||_2 ~ N sigma sqrt 2 (nscreen_const's delta); no room under 1/2: every quad
+template <int LOGN, int FB>
+__host__ __device__ inline double sparse_mu(double lvl, double amax, double sigma, double rho) {
+    constexpr double N = (double)(1 << LOGN);
+    if (!(sigma > 0.0)) return 0.0;
+    const double delta = kNScreenK * kScreenU * lvl * N * sigma * 1.4142135623730951 +
+                         kNScreenC * kScreenU * lvl * N * amax + kScreenSlicerU * kScreenU;
+    const double t = 0.5 - delta - 1.001 * (sparse_eps(1 << (FB / 2)) + rho);
+    const double sc = sigma * sqrt(N) * lvl;
+    return t > 0.0 ? 512.0 * erfc(t / (sc * 1.4142135623730951)) : 512.0;
+}
+
+// a wave's quads tested and sliced (wave-uniform; a wave's symbols: far below 2^32), and nothing at all in
+// the instantiations that test none
+template <bool SPARSE>
+struct QuadCounts {};
+template <>
+struct QuadCounts<true> {
+    unsigned tested = 0, sliced = 0;
+};
+
 template <typename R, int LOGN, int FB, int SCREEN = kLinkScreenNone>
 __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkArgs la) {
     static_assert(sizeof(R) == 8 && FB > 1 && !(FB & 1), "complex128 fixed square QAM");
     static_assert(uses_tt<R, LOGN, FB>() && Geo<LOGN>::TPS >= 64, "a symbol per wave, per-pass twiddles in LDS");
     static_assert(!SCREEN || Geo<LOGN>::TPS == 64, "the screen's ballot and its redo are one wave's");
+    constexpr bool NOISE_ALONE = SCREEN == kLinkScreenNoise || SCREEN == kLinkScreenSparse;
+    constexpr bool SPARSE = SCREEN == kLinkScreenSparse;
     constexpr int BLK = OFDM_LINK_BLOCK;
     using G = Geo<LOGN, BLK>;
     using C = cpx<R>;
@@ -264,6 +313,10 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
     [[maybe_unused]] ScreenSlicer<FB> fslicer;
     [[maybe_unused]] bool screen = false;
     [[maybe_unused]] float cz = 0, c0 = 0;
+    // kLinkScreenSparse: test each quad against T = (thr - e0) inv_lvl, or slice them all (the noise screen)
+    [[maybe_unused]] bool sparse = false;
+    [[maybe_unused]] float e0 = 0, inv_lvl = 0;
+    [[maybe_unused]] QuadCounts<SPARSE> quads;
     if constexpr (SCREEN == kLinkScreenTwo) {
         for (int i = threadIdx.x; i < 2 * TTS; i += BLK) tt32[i] = mk<float>((float)tt[i].re, (float)tt[i].im);
         double amax = 0;
@@ -281,7 +334,7 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
         screen = la.mode == OFDM_LINK_SCREEN_FORCED || !noise || sc.undecided < kScreenMaxUndecided;
         __syncthreads();
     }
-    if constexpr (SCREEN == kLinkScreenNoise) {
+    if constexpr (NOISE_ALONE) {
         // the forward twiddles only, and the float32 LUT times N (a power of two: the same rounding)
         for (int i = threadIdx.x; i < TTS; i += BLK) tt32[i] = mk<float>((float)tt[i].re, (float)tt[i].im);
         double amax = 0;
@@ -297,6 +350,31 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
         cz = sc.cz;
         c0 = sc.c0;
         screen = la.mode == OFDM_LINK_SCREEN_FORCED || !noise || sc.undecided < kNScreenMaxUndecided;
+        if constexpr (SPARSE) {
+            // rho: the largest distance of a table point from its own level under the slicer's constants,
+            // in double from the float32 values the screen adds and multiplies by -- lane e takes entry e
+            // (every wave the same); a point whose bits no level carries leaves no T at all
+            constexpr int SIDE = PermSlicer<FB>::SIDE;
+            const double lvl = (double)fslicer.mul.x * (double)(SIDE - 1);
+            const double offl = (double)fslicer.add.x * (double)(SIDE - 1);
+            double rho = 0;
+            for (int e = threadIdx.x % 64; e < (1 << FB); e += 64) {
+                const C v = lut_s[e];
+                const double pi = (double)((float)(1 << LOGN) * (float)v.re), pq = (double)((float)(1 << LOGN) * (float)v.im);
+                double ri = 1.0, rq = 1.0;
+                for (int k = 0; k < SIDE; ++k) {
+                    if (axis[0].ipat[k] == (e & (SIDE - 1))) ri = fabs(fma(pi, lvl, offl) - (double)k);
+                    if (axis[0].qpat[k] == (e >> (FB / 2))) rq = fabs(fma(pq, lvl, offl) - (double)k);
+                }
+                rho = fmax(rho, fmax(ri, rq));
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) rho = fmax(rho, __shfl_xor(rho, off, 64));
+            e0 = (float)(1.001 * (sparse_eps(SIDE) + rho));
+            inv_lvl = (float)(1.0 / lvl);
+            sparse = la.mode == OFDM_LINK_SCREEN_FORCED || !noise ||
+                     sparse_mu<LOGN, FB>(lvl, sqrt(amax), sigma_d, rho) < kSparseMaxPerQuad;
+        }
         __syncthreads();
     }
 
@@ -342,7 +420,17 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
 #pragma unroll
                             for (int i = 0; i < E; ++i) acc = __builtin_elementwise_fma(xf[i].v, xf[i].v, acc);
                         }
-                        static_for<0, E>([&](auto I) { xf[I].v += lut32[tb.template fixed<I>()].v; });
+                        // (kLinkScreenSparse on its tested path adds the point to the quads it slices, below;
+                        // OFDM_ABLATE_RX & 8, ablation builds only: neither the add nor the slicer -- a
+                        // timing build, its counts are wrong)
+                        if constexpr (SPARSE) {
+                            if (!sparse) static_for<0, E>([&](auto I) { xf[I].v += lut32[tb.template fixed<I>()].v; });
+                        } else {
+#if OFDM_ABLATION
+                            if (!(a.flags & 8))
+#endif
+                            static_for<0, E>([&](auto I) { xf[I].v += lut32[tb.template fixed<I>()].v; });
+                        }
                     }
                     float n2 = acc.x + acc.y;
 #pragma unroll
@@ -352,15 +440,61 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
                     const float thr = delta < 0.5f ? 0.5f - delta : -1.0f;
                     uint32_t bes = 0, ses = 0;
                     float m = 0.f;
-                    static_for<0, E / 4>([&](auto Q) {
-                        constexpr int q = Q;
-                        CF z[4];
+                    // (the parent's unrolled sequence stands twice below, so that the instantiations without the
+                    // test compile to the instructions they were: the compiler's register allocation follows
+                    // even unused locals)
+                    if constexpr (SPARSE) {
+                        if (sparse) {
+                            // a quad no component of which exceeds T, in any lane: d = 0 and m_quad <= thr, proven
+                            // (sparse_eps); thr < 0 (delta >= 1/2 or not finite) leaves T < 0: every quad sliced
+                            const float T = (thr - e0) * inv_lvl;
+                            static_for<0, E / 4>([&](auto Q) {
+                                constexpr int q = Q;
+                                float mx = 0.f;
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) z[j] = xf[4 * q + j];
-                        const uint32_t d = fslicer.diff_margin(z, lane_word(tb.lane, q), m);
-                        bes += __popc(d);
-                        ses += PermSlicer<FB>::nonzero_bytes(d);
-                    });
+                                for (int j = 0; j < 4; ++j)
+                                    mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(xf[4 * q + j].v.x),
+                                                                             __builtin_fabsf(xf[4 * q + j].v.y)));
+                                if (__ballot(!(mx <= T)) != 0) {  // (wave-uniform)
+                                    static_for<0, 4>([&](auto J) {
+                                        constexpr int i = 4 * q + J;
+                                        xf[i].v += lut32[tb.template fixed<i>()].v;
+                                    });
+                                    CF z[4];
+#pragma unroll
+                                    for (int j = 0; j < 4; ++j) z[j] = xf[4 * q + j];
+                                    const uint32_t d = fslicer.diff_margin(z, lane_word(tb.lane, q), m);
+                                    bes += __popc(d);
+                                    ses += PermSlicer<FB>::nonzero_bytes(d);
+                                    ++quads.sliced;
+                                }
+                            });
+                            quads.tested += E / 4;
+                        } else {
+                            static_for<0, E / 4>([&](auto Q) {
+                                constexpr int q = Q;
+                                CF z[4];
+#pragma unroll
+                                for (int j = 0; j < 4; ++j) z[j] = xf[4 * q + j];
+                                const uint32_t d = fslicer.diff_margin(z, lane_word(tb.lane, q), m);
+                                bes += __popc(d);
+                                ses += PermSlicer<FB>::nonzero_bytes(d);
+                            });
+                        }
+                    } else {
+#if OFDM_ABLATION
+                        if (!(a.flags & 8))
+#endif
+                        static_for<0, E / 4>([&](auto Q) {
+                            constexpr int q = Q;
+                            CF z[4];
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) z[j] = xf[4 * q + j];
+                            const uint32_t d = fslicer.diff_margin(z, lane_word(tb.lane, q), m);
+                            bes += __popc(d);
+                            ses += PermSlicer<FB>::nonzero_bytes(d);
+                        });
+                    }
                     redo = __ballot(!(m <= thr)) != 0;  // one undecided axis: the wave redoes the symbol
                     if (!redo) {
                         be += bes;
@@ -420,6 +554,14 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
                 if (screened) atomicAdd(&la.screen_counts[0], screened);
                 if (redone) atomicAdd(&la.screen_counts[1], redone);
             }
+            if constexpr (SPARSE) {  // uint64[4]: quads tested, quads sliced behind the screen's two
+                const unsigned long long qt = block_sum<unsigned long long, BLK>(t == 0 ? quads.tested : 0u, redc);
+                const unsigned long long qs = block_sum<unsigned long long, BLK>(t == 0 ? quads.sliced : 0u, redc);
+                if (threadIdx.x == 0) {
+                    if (qt) atomicAdd(&la.screen_counts[2], qt);
+                    if (qs) atomicAdd(&la.screen_counts[3], qs);
+                }
+            }
         }
     }
 }
@@ -443,7 +585,7 @@ static bool link_shape(const LinkArgs& a, int L) {
 }
 
 template <typename R, int LOGN>
-static hipError_t link_one(const LinkArgs& a, int L, bool noise_screen, int* grid, hipStream_t s) {
+static hipError_t link_one(const LinkArgs& a, int L, int screen, int* grid, hipStream_t s) {
     if constexpr (link_fb<R, LOGN>() > 0) {
         if (!link_shape<R, LOGN>(a, L)) return hipErrorInvalidValue;
         constexpr int FB = link_fb<R, LOGN>();
@@ -460,8 +602,9 @@ static hipError_t link_one(const LinkArgs& a, int L, bool noise_screen, int* gri
         };
         // screen off: the unscreened kernel itself, not the screened one with its decision forced
         if (a.mode == OFDM_LINK_SCREEN_OFF) return go(std::integral_constant<int, kLinkScreenNone>{});
-        return noise_screen ? go(std::integral_constant<int, kLinkScreenNoise>{})
-                            : go(std::integral_constant<int, kLinkScreenTwo>{});
+        if (screen == kLinkScreenSparse) return go(std::integral_constant<int, kLinkScreenSparse>{});
+        return screen == kLinkScreenNoise ? go(std::integral_constant<int, kLinkScreenNoise>{})
+                                          : go(std::integral_constant<int, kLinkScreenTwo>{});
     } else {
         return hipErrorInvalidValue;
     }
@@ -469,10 +612,10 @@ static hipError_t link_one(const LinkArgs& a, int L, bool noise_screen, int* gri
 
 // hipErrorInvalidValue: no fused form for this plan or these arguments (nothing launched)
 template <typename R>
-hipError_t launch_link(int logn, int L, const LinkArgs& a, bool noise_screen, int* grid, hipStream_t s) {
+hipError_t launch_link(int logn, int L, const LinkArgs& a, int screen, int* grid, hipStream_t s) {
 #define OFDM_LINK_CASE(LG) \
     case LG:               \
-        return link_one<R, LG>(a, L, noise_screen, grid, s);
+        return link_one<R, LG>(a, L, screen, grid, s);
     switch (logn) {
         OFDM_LOGN_CASES(OFDM_LINK_CASE)
         default:

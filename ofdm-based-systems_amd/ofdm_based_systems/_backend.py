@@ -29,9 +29,10 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib",
 # ABI 6: ofdm_rx_profile (the fused receiver with a per-subcarrier error / EVM record)
 # (ofdm_rx_sweep, the one-pass SNR sweep receiver, joined ABI 6 as an added entry point; so did
 # ofdm_link, the fused transmit + receive kernel, ofdm_link_screen, its two-transform float32 screen
-# with a mode and counts, and ofdm_link_nscreen, the same for the noise screen ofdm_link runs)
+# with a mode and counts, ofdm_link_nscreen, the same for the noise screen, and ofdm_link_sparse, the
+# noise screen slicing only the quads its noise can reach, which ofdm_link runs)
 ABI_VERSION = 6
-# ofdm_link_screen's and ofdm_link_nscreen's modes (OFDM_LINK_SCREEN_*, include/ofdm_hip.h)
+# ofdm_link_screen's, ofdm_link_nscreen's and ofdm_link_sparse's modes (OFDM_LINK_SCREEN_*, include/ofdm_hip.h)
 LINK_SCREEN_AUTO, LINK_SCREEN_OFF, LINK_SCREEN_FORCED = 0, 1, 2
 # SNR points one ofdm_rx_sweep call takes (OFDM_MAX_SWEEP_POINTS, include/ofdm_hip.h)
 MAX_SWEEP_POINTS = 40
@@ -126,6 +127,8 @@ SIGNATURES = {
     # (ofdm_link's arguments, mode, screen_counts)
     "ofdm_link_screen": (ctypes.c_int, [_VP, _VP, _U64, _VP, _I64, _F64, _I32, _I64, _I64, _I64, _VP, _I32, _VP]),
     "ofdm_link_nscreen": (ctypes.c_int, [_VP, _VP, _U64, _VP, _I64, _F64, _I32, _I64, _I64, _I64, _VP, _I32, _VP]),
+    # (ofdm_link's arguments, mode, sparse_counts: uint64[4])
+    "ofdm_link_sparse": (ctypes.c_int, [_VP, _VP, _U64, _VP, _I64, _F64, _I32, _I64, _I64, _I64, _VP, _I32, _VP]),
     # (plan, stream, bits, seed, sym0, n_sym, edges, n_edges, hist, sym_out, sym_keep; edges: a host
     # array of doubles, copied at the call)
     "ofdm_papr": (ctypes.c_int, [_VP, _VP, _VP, _U64, _I64, _I64, _c_f64p, _I32, _VP, _VP, _I64]),

@@ -251,14 +251,18 @@ class _Share:
 class LinkEngine:
     plan = None    # the libofdm_hip plan (set by __init__)
     _fused = None  # has_fused, asked of the library once per engine
-    # the fused link's float32 screens (link()): everything None = ofdm_link (the noise screen, automatic).
-    # screen_mode, a B.LINK_SCREEN_* mode = ofdm_link_screen (the two-transform screen), counting into
-    # screen_counts (device int64 [2], or None); nscreen_mode / nscreen_counts = the same for
-    # ofdm_link_nscreen (the noise screen).  One pair at a time; the counts of a run do not depend on any.
+    # the fused link's float32 screens (link()): everything None = ofdm_link (the noise screen with the
+    # sparse slicer, automatic).  screen_mode, a B.LINK_SCREEN_* mode = ofdm_link_screen (the two-transform
+    # screen), counting into screen_counts (device int64 [2], or None); nscreen_mode / nscreen_counts = the
+    # same for ofdm_link_nscreen (the noise screen); sparse_mode / sparse_counts (device int64 [4]: symbols
+    # screened, redone, quads tested, sliced) for ofdm_link_sparse.  One pair at a time; the counts of a
+    # run do not depend on any.
     screen_mode = None
     screen_counts = None
     nscreen_mode = None
     nscreen_counts = None
+    sparse_mode = None
+    sparse_counts = None
     # the soft limiter (ofdm_tx_clip): the level in dB above nominal_power, and the threshold on |x|^2
     # handed to the library; None = no limiter, ofdm_tx as before
     clip_db = None
@@ -375,19 +379,24 @@ class LinkEngine:
         the registers; ``stats`` holds the whole stream's record (a power pass, :meth:`tx` with y = None).
         With :attr:`screen_mode` set (B.LINK_SCREEN_*), ofdm_link_screen in that mode, adding to
         :attr:`screen_counts` (device int64 [2]: symbols screened, symbols redone) when that is set;
-        with :attr:`nscreen_mode` set, ofdm_link_nscreen and :attr:`nscreen_counts` likewise.  Setting
-        anything of both pairs is an error."""
+        with :attr:`nscreen_mode` set, ofdm_link_nscreen and :attr:`nscreen_counts` likewise; with
+        :attr:`sparse_mode` set, ofdm_link_sparse and :attr:`sparse_counts` (device int64 [4]).  Setting
+        anything of more than one pair is an error."""
         two = self.screen_mode is not None or self.screen_counts is not None
         noise = self.nscreen_mode is not None or self.nscreen_counts is not None
-        if two and noise:
-            raise ValueError("screen_mode / screen_counts (ofdm_link_screen) and nscreen_mode / nscreen_counts "
-                             "(ofdm_link_nscreen) are set together: one screen at a time")
+        sparse = self.sparse_mode is not None or self.sparse_counts is not None
+        if two + noise + sparse > 1:
+            raise ValueError("screen_mode / screen_counts (ofdm_link_screen), nscreen_mode / nscreen_counts "
+                             "(ofdm_link_nscreen) and sparse_mode / sparse_counts (ofdm_link_sparse) are set "
+                             "together: one screen at a time")
         args = (self.plan.handle, stream, int(seed), B.ptr(stats), int(total_samples), float(snr_db), int(noise_on),
                 int(sym0), int(n_sym), int(n_valid), B.ptr(counters))
         if self.screen_mode is not None:
             B.check(self._lib.ofdm_link_screen(*args, int(self.screen_mode), B.ptr(self.screen_counts)))
         elif self.nscreen_mode is not None:
             B.check(self._lib.ofdm_link_nscreen(*args, int(self.nscreen_mode), B.ptr(self.nscreen_counts)))
+        elif self.sparse_mode is not None:
+            B.check(self._lib.ofdm_link_sparse(*args, int(self.sparse_mode), B.ptr(self.sparse_counts)))
         else:
             B.check(self._lib.ofdm_link(*args))
 
