@@ -1009,6 +1009,12 @@ static int link_call(int screen, ofdm_plan_t p, void* stream, uint64_t seed, con
     return OFDM_OK;
 }
 
+// the mode of the entry points that take one (name: the entry point's, for the message)
+static int link_mode_ok(const char* name, int32_t mode) {
+    if (mode == OFDM_LINK_SCREEN_AUTO || mode == OFDM_LINK_SCREEN_OFF || mode == OFDM_LINK_SCREEN_FORCED) return OFDM_OK;
+    return fail(OFDM_E_INVALID, std::string(name) + ": mode " + std::to_string(mode) + " is not an OFDM_LINK_SCREEN_* value");
+}
+
 int ofdm_link(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
               double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym, int64_t n_valid_bits,
               uint64_t* counters) {
@@ -1019,8 +1025,7 @@ int ofdm_link(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stats* stat
 int ofdm_link_sparse(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
                      double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym, int64_t n_valid_bits,
                      uint64_t* counters, int32_t mode, uint64_t* sparse_counts) {
-    if (mode != OFDM_LINK_SCREEN_AUTO && mode != OFDM_LINK_SCREEN_OFF && mode != OFDM_LINK_SCREEN_FORCED)
-        return fail(OFDM_E_INVALID, "ofdm_link_sparse: mode " + std::to_string(mode) + " is not an OFDM_LINK_SCREEN_* value");
+    if (const int rc = link_mode_ok("ofdm_link_sparse", mode)) return rc;
     // off: the noise screen itself in its automatic mode, and nothing counted
     if (mode == OFDM_LINK_SCREEN_OFF)
         return link_call(kLinkScreenNoise, p, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits,
@@ -1032,8 +1037,7 @@ int ofdm_link_sparse(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stat
 int ofdm_link_nscreen(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
                       double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym, int64_t n_valid_bits,
                       uint64_t* counters, int32_t mode, uint64_t* screen_counts) {
-    if (mode != OFDM_LINK_SCREEN_AUTO && mode != OFDM_LINK_SCREEN_OFF && mode != OFDM_LINK_SCREEN_FORCED)
-        return fail(OFDM_E_INVALID, "ofdm_link_nscreen: mode " + std::to_string(mode) + " is not an OFDM_LINK_SCREEN_* value");
+    if (const int rc = link_mode_ok("ofdm_link_nscreen", mode)) return rc;
     return link_call(kLinkScreenNoise, p, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits,
                      counters, mode, screen_counts);
 }
@@ -1041,8 +1045,7 @@ int ofdm_link_nscreen(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_sta
 int ofdm_link_screen(ofdm_plan_t p, void* stream, uint64_t seed, const ofdm_stats* stats, int64_t total_samples,
                      double snr_db, int32_t noise_on, int64_t sym0, int64_t n_sym, int64_t n_valid_bits,
                      uint64_t* counters, int32_t mode, uint64_t* screen_counts) {
-    if (mode != OFDM_LINK_SCREEN_AUTO && mode != OFDM_LINK_SCREEN_OFF && mode != OFDM_LINK_SCREEN_FORCED)
-        return fail(OFDM_E_INVALID, "ofdm_link_screen: mode " + std::to_string(mode) + " is not an OFDM_LINK_SCREEN_* value");
+    if (const int rc = link_mode_ok("ofdm_link_screen", mode)) return rc;
     return link_call(kLinkScreenTwo, p, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits,
                      counters, mode, screen_counts);
 }

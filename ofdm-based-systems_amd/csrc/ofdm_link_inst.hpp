@@ -42,6 +42,13 @@
 // chain and a ballot per quad.  The counts, the symbols redone and the screen's counts are the noise
 // screen's for every input.  Whether a launch tests its quads or runs the noise screen's unrolled
 // sequence is a workgroup-uniform decision beside `screen` (sparse_mu below).
+//
+// The three screens share their text: one prologue (the tables, the slicer, the constants and the decision;
+// the sparse part behind it), one quad-slicing statement (`slice` in the screened symbol, called per tested
+// quad or for all four), one table-point add (AddPoint) and one undecided-axes formula (undecided_axes).
+// SCREEN = none, Two and Noise compile to the instructions they had with a copy each
+// (profiles/link_refactor_kernel_audit.txt); the symbol loop stays inline for the same reason -- a lambda
+// or a function around the screened symbol, even one never called, moves all four kernels' registers.
 #pragma once
 
 #include "ofdm_kernels_inst.hpp"
@@ -146,31 +153,35 @@ struct ScreenSlicer : PermSlicer<FB> {
 };
 
 // The screen's constants of a launch: delta in levels = cz ||z32||_2 + c0 (screen_bound above times
-// the level multiplier, plus the slicer's own roundings), and the expected undecided axes per symbol.
+// the level multiplier, plus the slicer's own roundings), and, under noise, delta at the expected norm and
+// the expected undecided axes per symbol there.
 struct ScreenConst {
     float cz, c0;
-    double undecided;
+    double delta = 0.0, undecided = 0.0;
+    // kz, k0: the two constants in double (1.001: the float rounding of the two and of cz sqrt(n2) + c0 itself)
+    __host__ __device__ ScreenConst(double kz, double k0) : cz((float)(1.001 * kz)), c0((float)(1.001 * k0)) {}
 };
+// An axis is undecided when its coordinate lies within delta of one of the side - 1 boundaries; under noise
+// of deviation sc levels the coordinate's density there is phi(1/2 / sc) / sc from each of the two levels
+// beside it, each sent with probability 1 / side.
+template <int LOGN, int FB>
+__host__ __device__ inline double undecided_axes(double delta, double sc) {
+    constexpr double N = (double)(1 << LOGN), side = (double)(1 << (FB / 2));
+    const double phi = exp(-0.125 / (sc * sc)) * 0.3989422804014327 / sc;
+    return 2.0 * N * (side - 1.0) * (2.0 / side) * 2.0 * delta * phi;
+}
 // lvl: levels per unit of z (the slicer's multiplier times side - 1); amax: the folded LUT's largest
 // modulus; p: the stream's mean sample power; sigma: the noise's per-component deviation
 template <int LOGN, int FB>
 __host__ __device__ inline ScreenConst screen_const(double lvl, double amax, double p, double sigma) {
-    constexpr double N = (double)(1 << LOGN), side = (double)(1 << (FB / 2));
+    constexpr double N = (double)(1 << LOGN);
     const double rootn = sqrt(N);
     const double kz = kScreenK * kScreenU * lvl;
-    ScreenConst c;
-    // (1.001: the float rounding of the two constants and of cz sqrt(n2) + c0 itself)
-    c.cz = (float)(1.001 * kz);
-    c.c0 = (float)(1.001 * (kz * N * rootn * amax + kScreenSlicerU * kScreenU));
-    // An axis is undecided when its coordinate lies within delta of one of the side - 1 boundaries;
-    // under noise of deviation sc levels the coordinate's density there is phi(1/2 / sc) / sc from each of
-    // the two levels beside it, each sent with probability 1 / side.  ||z||_2 ~ N sqrt(p + 2 sigma^2).
-    c.undecided = 0.0;
-    if (sigma > 0.0) {
+    ScreenConst c(kz, kz * N * rootn * amax + kScreenSlicerU * kScreenU);
+    if (sigma > 0.0) {  // ||z||_2 ~ N sqrt(p + 2 sigma^2)
         const double sc = sigma * rootn * lvl;
-        const double delta = kz * (N * sqrt(p + 2.0 * sigma * sigma) + N * rootn * amax) + kScreenSlicerU * kScreenU;
-        const double phi = exp(-0.125 / (sc * sc)) * 0.3989422804014327 / sc;
-        c.undecided = 2.0 * N * (side - 1.0) * (2.0 / side) * 2.0 * delta * phi;
+        c.delta = kz * (N * sqrt(p + 2.0 * sigma * sigma) + N * rootn * amax) + kScreenSlicerU * kScreenU;
+        c.undecided = undecided_axes<LOGN, FB>(c.delta, sc);
     }
     return c;
 }
@@ -195,18 +206,14 @@ constexpr double kNScreenMaxUndecided = 0.5;
 // delta in levels = cz ||ghat||_2 + c0, and the expected undecided axes per symbol (||ghat||_2 ~ N sigma sqrt 2)
 template <int LOGN, int FB>
 __host__ __device__ inline ScreenConst nscreen_const(double lvl, double amax, double sigma) {
-    constexpr double N = (double)(1 << LOGN), side = (double)(1 << (FB / 2));
+    constexpr double N = (double)(1 << LOGN);
     const double kz = kNScreenK * kScreenU * lvl;
     const double k0 = kNScreenC * kScreenU * lvl * N * amax + kScreenSlicerU * kScreenU;
-    ScreenConst c;
-    c.cz = (float)(1.001 * kz);
-    c.c0 = (float)(1.001 * k0);
-    c.undecided = 0.0;
+    ScreenConst c(kz, k0);
     if (sigma > 0.0) {
         const double sc = sigma * sqrt(N) * lvl;
-        const double delta = kz * N * sigma * 1.4142135623730951 + k0;
-        const double phi = exp(-0.125 / (sc * sc)) * 0.3989422804014327 / sc;
-        c.undecided = 2.0 * N * (side - 1.0) * (2.0 / side) * 2.0 * delta * phi;
+        c.delta = kz * N * sigma * 1.4142135623730951 + k0;
+        c.undecided = undecided_axes<LOGN, FB>(c.delta, sc);
     }
     return c;
 }
@@ -229,15 +236,12 @@ constexpr double sparse_eps(int side) { return (1.5 * side + 6.0) * kScreenU; }
 // from 22 dB (mu = 3.1, 0.95 sliced: 1.811 against 1.729) -- a sliced quad pays its test and the branch
 constexpr double kSparseMaxPerQuad = 2.0;
 // mu = 8 * 64 * 2 Q(T_levels / sigma_c): sigma_c the noise's deviation per component in levels, T_levels at
-// the expected norm ||ghat||_2 ~ N sigma sqrt 2 (nscreen_const's delta); no room under 1/2: every quad
+// delta, nscreen_const's at the expected norm ||ghat||_2 ~ N sigma sqrt 2; no room under 1/2: every quad
 template <int LOGN, int FB>
-__host__ __device__ inline double sparse_mu(double lvl, double amax, double sigma, double rho) {
-    constexpr double N = (double)(1 << LOGN);
+__host__ __device__ inline double sparse_mu(double lvl, double sigma, double delta, double rho) {
     if (!(sigma > 0.0)) return 0.0;
-    const double delta = kNScreenK * kScreenU * lvl * N * sigma * 1.4142135623730951 +
-                         kNScreenC * kScreenU * lvl * N * amax + kScreenSlicerU * kScreenU;
     const double t = 0.5 - delta - 1.001 * (sparse_eps(1 << (FB / 2)) + rho);
-    const double sc = sigma * sqrt(N) * lvl;
+    const double sc = sigma * sqrt((double)(1 << LOGN)) * lvl;
     return t > 0.0 ? 512.0 * erfc(t / (sc * 1.4142135623730951)) : 512.0;
 }
 
@@ -248,6 +252,16 @@ struct QuadCounts {};
 template <>
 struct QuadCounts<true> {
     unsigned tested = 0, sliced = 0;
+};
+
+// the noise screens: xf[I] += the table point N l32 of element I's subcarrier (static_for's body)
+template <int E, typename TB>
+struct AddPoint {
+    cpx<float> (&xf)[E];
+    const cpx<float>* lut32;
+    const TB& tb;
+    template <typename I>
+    __device__ __forceinline__ void operator()(I) const { xf[I::value].v += lut32[tb.template fixed<I::value>()].v; }
 };
 
 template <typename R, int LOGN, int FB, int SCREEN = kLinkScreenNone>
@@ -317,50 +331,36 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
     [[maybe_unused]] bool sparse = false;
     [[maybe_unused]] float e0 = 0, inv_lvl = 0;
     [[maybe_unused]] QuadCounts<SPARSE> quads;
-    if constexpr (SCREEN == kLinkScreenTwo) {
-        for (int i = threadIdx.x; i < 2 * TTS; i += BLK) tt32[i] = mk<float>((float)tt[i].re, (float)tt[i].im);
+    if constexpr (SCREEN) {
+        // kLinkScreenTwo: both twiddle tables and the LUT as it is; the noise screens: the forward twiddles
+        // only, and the LUT times N (a power of two: the same rounding)
+        constexpr int SIDE = PermSlicer<FB>::SIDE;
+        constexpr float POINT = NOISE_ALONE ? (float)(1 << LOGN) : 1.f;
+        for (int i = threadIdx.x; i < (NOISE_ALONE ? 1 : 2) * TTS; i += BLK) tt32[i] = mk<float>((float)tt[i].re, (float)tt[i].im);
         double amax = 0;
         for (int i = 0; i < (1 << FB); ++i) {
             const C v = lut_s[i];
             amax = fmax(amax, v.re * v.re + v.im * v.im);
-            if (i == (int)threadIdx.x) lut32[i] = mk<float>((float)v.re, (float)v.im);
+            if (i == (int)threadIdx.x) lut32[i] = mk<float>(POINT * (float)v.re, POINT * (float)v.im);
         }
         static_assert((1 << FB) <= BLK, "one LUT entry per thread");
         fslicer.load(axis[0], cm.scale);
-        const ScreenConst sc = screen_const<LOGN, FB>((double)fslicer.mul.x * (double)(PermSlicer<FB>::SIDE - 1),
-                                                      sqrt(amax), power, sigma_d);
+        const double lvl = (double)fslicer.mul.x * (double)(SIDE - 1);
+        const ScreenConst sc = NOISE_ALONE ? nscreen_const<LOGN, FB>(lvl, sqrt(amax), sigma_d)
+                                           : screen_const<LOGN, FB>(lvl, sqrt(amax), power, sigma_d);
         cz = sc.cz;
         c0 = sc.c0;
-        screen = la.mode == OFDM_LINK_SCREEN_FORCED || !noise || sc.undecided < kScreenMaxUndecided;
+        screen = la.mode == OFDM_LINK_SCREEN_FORCED || !noise ||
+                 sc.undecided < (NOISE_ALONE ? kNScreenMaxUndecided : kScreenMaxUndecided);
         __syncthreads();
-    }
-    if constexpr (NOISE_ALONE) {
-        // the forward twiddles only, and the float32 LUT times N (a power of two: the same rounding)
-        for (int i = threadIdx.x; i < TTS; i += BLK) tt32[i] = mk<float>((float)tt[i].re, (float)tt[i].im);
-        double amax = 0;
-        for (int i = 0; i < (1 << FB); ++i) {
-            const C v = lut_s[i];
-            amax = fmax(amax, v.re * v.re + v.im * v.im);
-            if (i == (int)threadIdx.x) lut32[i] = mk<float>((float)(1 << LOGN) * (float)v.re, (float)(1 << LOGN) * (float)v.im);
-        }
-        static_assert((1 << FB) <= BLK, "one LUT entry per thread");
-        fslicer.load(axis[0], cm.scale);
-        const ScreenConst sc = nscreen_const<LOGN, FB>((double)fslicer.mul.x * (double)(PermSlicer<FB>::SIDE - 1),
-                                                       sqrt(amax), sigma_d);
-        cz = sc.cz;
-        c0 = sc.c0;
-        screen = la.mode == OFDM_LINK_SCREEN_FORCED || !noise || sc.undecided < kNScreenMaxUndecided;
         if constexpr (SPARSE) {
             // rho: the largest distance of a table point from its own level under the slicer's constants,
             // in double from the float32 values the screen adds and multiplies by -- lane e takes entry e
             // (every wave the same); a point whose bits no level carries leaves no T at all
-            constexpr int SIDE = PermSlicer<FB>::SIDE;
-            const double lvl = (double)fslicer.mul.x * (double)(SIDE - 1);
             const double offl = (double)fslicer.add.x * (double)(SIDE - 1);
             double rho = 0;
             for (int e = threadIdx.x % 64; e < (1 << FB); e += 64) {
-                const C v = lut_s[e];
-                const double pi = (double)((float)(1 << LOGN) * (float)v.re), pq = (double)((float)(1 << LOGN) * (float)v.im);
+                const double pi = (double)lut32[e].re, pq = (double)lut32[e].im;
                 double ri = 1.0, rq = 1.0;
                 for (int k = 0; k < SIDE; ++k) {
                     if (axis[0].ipat[k] == (e & (SIDE - 1))) ri = fabs(fma(pi, lvl, offl) - (double)k);
@@ -373,9 +373,8 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
             e0 = (float)(1.001 * (sparse_eps(SIDE) + rho));
             inv_lvl = (float)(1.0 / lvl);
             sparse = la.mode == OFDM_LINK_SCREEN_FORCED || !noise ||
-                     sparse_mu<LOGN, FB>(lvl, sqrt(amax), sigma_d, rho) < kSparseMaxPerQuad;
+                     sparse_mu<LOGN, FB>(lvl, sigma_d, sc.delta, rho) < kSparseMaxPerQuad;
         }
-        __syncthreads();
     }
 
     const int64_t niter = (cm.n_sym + G::SPB - 1) / G::SPB;
@@ -396,6 +395,7 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
                     tb.load(cm, sg, t, nullptr, true);
                     CF xf[E];
                     f32x2 acc = f32x2{0.f, 0.f};
+                    using Add = AddPoint<E, TxBits<FB, TPS>>;
                     if constexpr (SCREEN == kLinkScreenTwo) {
                         static_for<0, E>([&](auto I) { xf[I] = lut32[tb.template fixed<I>()]; });
                         fft_sym<float, LOGN, true, FB>(xf, rowf, tt32, tt32 + TTS, t);
@@ -423,14 +423,10 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
                         // (kLinkScreenSparse on its tested path adds the point to the quads it slices, below;
                         // OFDM_ABLATE_RX & 8, ablation builds only: neither the add nor the slicer -- a
                         // timing build, its counts are wrong)
-                        if constexpr (SPARSE) {
-                            if (!sparse) static_for<0, E>([&](auto I) { xf[I].v += lut32[tb.template fixed<I>()].v; });
-                        } else {
 #if OFDM_ABLATION
-                            if (!(a.flags & 8))
+                        if (!(a.flags & 8))
 #endif
-                            static_for<0, E>([&](auto I) { xf[I].v += lut32[tb.template fixed<I>()].v; });
-                        }
+                        if (!SPARSE || !sparse) static_for<0, E>(Add{xf, lut32, tb});
                     }
                     float n2 = acc.x + acc.y;
 #pragma unroll
@@ -440,9 +436,16 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
                     const float thr = delta < 0.5f ? 0.5f - delta : -1.0f;
                     uint32_t bes = 0, ses = 0;
                     float m = 0.f;
-                    // (the parent's unrolled sequence stands twice below, so that the instantiations without the
-                    // test compile to the instructions they were: the compiler's register allocation follows
-                    // even unused locals)
+                    // quad Q of every lane sliced: its difference word counted, its margin into m
+                    const auto slice = [&](auto Q) {
+                        constexpr int q = Q;
+                        CF z[4];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) z[j] = xf[4 * q + j];
+                        const uint32_t d = fslicer.diff_margin(z, lane_word(tb.lane, q), m);
+                        bes += __popc(d);
+                        ses += PermSlicer<FB>::nonzero_bytes(d);
+                    };
                     if constexpr (SPARSE) {
                         if (sparse) {
                             // a quad no component of which exceeds T, in any lane: d = 0 and m_quad <= thr, proven
@@ -456,45 +459,20 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
                                     mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(xf[4 * q + j].v.x),
                                                                              __builtin_fabsf(xf[4 * q + j].v.y)));
                                 if (__ballot(!(mx <= T)) != 0) {  // (wave-uniform)
-                                    static_for<0, 4>([&](auto J) {
-                                        constexpr int i = 4 * q + J;
-                                        xf[i].v += lut32[tb.template fixed<i>()].v;
-                                    });
-                                    CF z[4];
-#pragma unroll
-                                    for (int j = 0; j < 4; ++j) z[j] = xf[4 * q + j];
-                                    const uint32_t d = fslicer.diff_margin(z, lane_word(tb.lane, q), m);
-                                    bes += __popc(d);
-                                    ses += PermSlicer<FB>::nonzero_bytes(d);
+                                    static_for<4 * q, 4 * q + 4>(Add{xf, lut32, tb});
+                                    slice(Q);
                                     ++quads.sliced;
                                 }
                             });
                             quads.tested += E / 4;
-                        } else {
-                            static_for<0, E / 4>([&](auto Q) {
-                                constexpr int q = Q;
-                                CF z[4];
-#pragma unroll
-                                for (int j = 0; j < 4; ++j) z[j] = xf[4 * q + j];
-                                const uint32_t d = fslicer.diff_margin(z, lane_word(tb.lane, q), m);
-                                bes += __popc(d);
-                                ses += PermSlicer<FB>::nonzero_bytes(d);
-                            });
                         }
-                    } else {
-#if OFDM_ABLATION
-                        if (!(a.flags & 8))
-#endif
-                        static_for<0, E / 4>([&](auto Q) {
-                            constexpr int q = Q;
-                            CF z[4];
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) z[j] = xf[4 * q + j];
-                            const uint32_t d = fslicer.diff_margin(z, lane_word(tb.lane, q), m);
-                            bes += __popc(d);
-                            ses += PermSlicer<FB>::nonzero_bytes(d);
-                        });
                     }
+                    // (the test stays outside the quad loop: four uniform branches on `sparse` inside it cost the
+                    // untested path 2 to 4 %, profiles/link_refactor_ab.txt)
+#if OFDM_ABLATION
+                    if (!(a.flags & 8))
+#endif
+                    if (!SPARSE || !sparse) static_for<0, E / 4>(slice);
                     redo = __ballot(!(m <= thr)) != 0;  // one undecided axis: the wave redoes the symbol
                     if (!redo) {
                         be += bes;
@@ -601,10 +579,12 @@ static hipError_t link_one(const LinkArgs& a, int L, int screen, int* grid, hipS
                                                    rx_grid_rounds<R, FB, LOGN>(), a.r.c.n_sym, a, grid, s);
         };
         // screen off: the unscreened kernel itself, not the screened one with its decision forced
-        if (a.mode == OFDM_LINK_SCREEN_OFF) return go(std::integral_constant<int, kLinkScreenNone>{});
-        if (screen == kLinkScreenSparse) return go(std::integral_constant<int, kLinkScreenSparse>{});
-        return screen == kLinkScreenNoise ? go(std::integral_constant<int, kLinkScreenNoise>{})
-                                          : go(std::integral_constant<int, kLinkScreenTwo>{});
+        switch (a.mode == OFDM_LINK_SCREEN_OFF ? kLinkScreenNone : screen) {
+            case kLinkScreenNone: return go(std::integral_constant<int, kLinkScreenNone>{});
+            case kLinkScreenSparse: return go(std::integral_constant<int, kLinkScreenSparse>{});
+            case kLinkScreenNoise: return go(std::integral_constant<int, kLinkScreenNoise>{});
+            default: return go(std::integral_constant<int, kLinkScreenTwo>{});
+        }
     } else {
         return hipErrorInvalidValue;
     }

@@ -263,6 +263,10 @@ class LinkEngine:
     nscreen_counts = None
     sparse_mode = None
     sparse_counts = None
+    # (mode attribute, counts attribute, library function), in link()'s order
+    _LINK_SCREENS = (("screen_mode", "screen_counts", "ofdm_link_screen"),
+                     ("nscreen_mode", "nscreen_counts", "ofdm_link_nscreen"),
+                     ("sparse_mode", "sparse_counts", "ofdm_link_sparse"))
     # the soft limiter (ofdm_tx_clip): the level in dB above nominal_power, and the threshold on |x|^2
     # handed to the library; None = no limiter, ofdm_tx as before
     clip_db = None
@@ -382,23 +386,18 @@ class LinkEngine:
         with :attr:`nscreen_mode` set, ofdm_link_nscreen and :attr:`nscreen_counts` likewise; with
         :attr:`sparse_mode` set, ofdm_link_sparse and :attr:`sparse_counts` (device int64 [4]).  Setting
         anything of more than one pair is an error."""
-        two = self.screen_mode is not None or self.screen_counts is not None
-        noise = self.nscreen_mode is not None or self.nscreen_counts is not None
-        sparse = self.sparse_mode is not None or self.sparse_counts is not None
-        if two + noise + sparse > 1:
+        pairs = [(getattr(self, mode), getattr(self, counts), fn) for mode, counts, fn in self._LINK_SCREENS]
+        if sum(mode is not None or counts is not None for mode, counts, _ in pairs) > 1:
             raise ValueError("screen_mode / screen_counts (ofdm_link_screen), nscreen_mode / nscreen_counts "
                              "(ofdm_link_nscreen) and sparse_mode / sparse_counts (ofdm_link_sparse) are set "
                              "together: one screen at a time")
         args = (self.plan.handle, stream, int(seed), B.ptr(stats), int(total_samples), float(snr_db), int(noise_on),
                 int(sym0), int(n_sym), int(n_valid), B.ptr(counters))
-        if self.screen_mode is not None:
-            B.check(self._lib.ofdm_link_screen(*args, int(self.screen_mode), B.ptr(self.screen_counts)))
-        elif self.nscreen_mode is not None:
-            B.check(self._lib.ofdm_link_nscreen(*args, int(self.nscreen_mode), B.ptr(self.nscreen_counts)))
-        elif self.sparse_mode is not None:
-            B.check(self._lib.ofdm_link_sparse(*args, int(self.sparse_mode), B.ptr(self.sparse_counts)))
-        else:
-            B.check(self._lib.ofdm_link(*args))
+        for mode, counts, fn in pairs:
+            if mode is not None:
+                B.check(getattr(self._lib, fn)(*args, int(mode), B.ptr(counts)))
+                return
+        B.check(self._lib.ofdm_link(*args))
 
     def papr_hist(self, stream, bits_d, seed, sym0, n_sym, edges, hist, sym_out=None, sym_keep=0):
         """ofdm_papr: bin the per-symbol PAPR of symbols [sym0, sym0 + n_sym) at ``edges`` (linear ratios,

@@ -82,11 +82,12 @@ def fft32(x):
     return a
 
 
-def model(snr_db, symbols, seed=1, n_fft=1024):
+def draw(snr_db, symbols, seed=1, n_fft=1024):
     """64-QAM at unit power over a flat unit channel; the noise as Mwc64x forms it (a float32 radius times
     a float32 entry of 64 phases: exact in double on the complex128 side, rounded once on the screen's).
-    Returns (kept, wrong_kept): the mask of symbols the screen keeps, and how many kept symbols hold an
-    element whose float32 level differs from the float64 one."""
+    Returns the drawn level indices (ii, qq), the complex128 spectrum z64, the screen's transformed noise
+    ghat and spectrum zhat, and its bound delta per symbol in levels (model and link_sparse_expect.model
+    share the draw: the same generator calls in the same order)."""
     rng = np.random.default_rng(seed)
     lev = np.arange(-7, 8, 2) / math.sqrt(42)
     step, amax = 2 / math.sqrt(42), math.sqrt(98 / 42)
@@ -98,12 +99,21 @@ def model(snr_db, symbols, seed=1, n_fft=1024):
     th = (2 * rng.integers(0, 64, (symbols, n_fft)) + 1) / 64 * np.pi
     er, ei = sigma * np.cos(th).astype(np.float32), sigma * np.sin(th).astype(np.float32)
     z64 = np.fft.fft(x + (r.astype(np.float64) * er + 1j * (r.astype(np.float64) * ei)), axis=1)
-    # the screen: once-rounded products, one float32 transform, the point added, the margin
+    # the screen: once-rounded products, one float32 transform, the point added
     ghat = fft32(((r * er) + 1j * (r * ei)).astype(np.complex64))
     zhat = (ghat + (lut * n_fft).astype(np.complex64)).astype(np.complex64)
     gn = np.linalg.norm(ghat.astype(np.complex128), axis=1)
     lvl = 1 / (step * math.sqrt(n_fft))                           # levels per unit of unnormalised z
     delta = (delta_sym(gn / math.sqrt(n_fft), amax) * math.sqrt(n_fft)) * lvl + SLICER_U * U
+    return ii, qq, z64, ghat, zhat, delta
+
+
+def model(snr_db, symbols, seed=1, n_fft=1024):
+    """The screen on draw()'s symbols, with its margin.  Returns (kept, wrong_kept): the mask of symbols the
+    screen keeps, and how many kept symbols hold an element whose float32 level differs from the float64
+    one."""
+    _, _, z64, _, zhat, delta = draw(snr_db, symbols, seed, n_fft)
+    lvl = 1 / (2 / math.sqrt(42) * math.sqrt(n_fft))
 
     def levels(z):
         y = np.clip(np.stack([z.real, z.imag]) * lvl + 3.5, 0, 7)

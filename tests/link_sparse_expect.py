@@ -78,27 +78,13 @@ def sparse_rule(snr_db, noise_on=True):
 
 
 def model(snr_db, symbols, seed=1, n_fft=1024):
-    """link_nscreen_expect.model's symbols and noise (the same generator calls in the same order), with the
+    """link_nscreen_expect.draw's symbols, noise and bound (the noise screen's model runs on the same), with the
     quads of the sparse slicer: components k = 256 q .. 256 q + 255 stand for quad q (the property is one
     of each component, so the grouping only sets how many quads are skipped).  Returns the number of quads,
     of skipped quads, and of skipped quads that hold an element whose float64 decision differs from the
     transmitted level, whose float32 decision does, or whose float32 margin exceeds thr."""
-    rng = np.random.default_rng(seed)
-    lev = np.arange(-7, 8, 2) / math.sqrt(42)
-    step, amax = 2 / math.sqrt(42), math.sqrt(98 / 42)
-    ii, qq = rng.integers(0, 8, (symbols, n_fft)), rng.integers(0, 8, (symbols, n_fft))
-    lut = (lev[ii] + 1j * lev[qq]) / math.sqrt(n_fft)
-    x = np.fft.ifft(lut, axis=1) * n_fft
-    sigma = np.float32(math.sqrt(1 / 10 ** (snr_db / 10) / 2))
-    r = np.sqrt(-2 * np.log(1 - rng.random((symbols, n_fft)))).astype(np.float32)
-    th = (2 * rng.integers(0, 64, (symbols, n_fft)) + 1) / 64 * np.pi
-    er, ei = sigma * np.cos(th).astype(np.float32), sigma * np.sin(th).astype(np.float32)
-    z64 = np.fft.fft(x + (r.astype(np.float64) * er + 1j * (r.astype(np.float64) * ei)), axis=1)
-    ghat = NX.fft32(((r * er) + 1j * (r * ei)).astype(np.complex64))
-    zhat = (ghat + (lut * n_fft).astype(np.complex64)).astype(np.complex64)
-    gn = np.linalg.norm(ghat.astype(np.complex128), axis=1)
+    ii, qq, z64, ghat, zhat, delta = NX.draw(snr_db, symbols, seed, n_fft)
     lvl, off = slicer_constants(n_fft)
-    delta = (NX.delta_sym(gn / math.sqrt(n_fft), amax) * math.sqrt(n_fft)) * (1 / (step * math.sqrt(n_fft))) + NX.SLICER_U * U
     thr = np.where(delta < 0.5, 0.5 - delta, -1.0)
     t = np.array([threshold(d) for d in delta])
 
