@@ -31,15 +31,11 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
-// (kNotInBuild: a dispatch that reached a shape an OFDM_AB_ONLY experiment build does not
-// instantiate -- reported as a bad argument naming the build, not as a HIP error)
+// A direct HIP API call (or a launcher that has no verdict of its own), named by its own text; the
+// launchers that answer the sentinels of ofdm_launch.hpp go through checked() below
 #define HIPCHK(expr)                                                                       \
     do {                                                                                   \
         hipError_t _e = (expr);                                                            \
-        if (kAbOnly && _e == kNotInBuild)                                                  \
-            return fail(OFDM_E_INVALID, std::string(#expr ": kernel not in this build (an "  \
-                                                    "OFDM_AB_ONLY variant instantiates "     \
-                                                    "N = 1024..4096 only)"));               \
         if (_e != hipSuccess)                                                              \
             return fail(OFDM_E_HIP, std::string(#expr ": ") + hipGetErrorString(_e));      \
     } while (0)
@@ -266,6 +262,35 @@ int log2_exact(int n) {
 // misalignment of the symbol start, one slack word for the 64-bit extraction window,
 // rounded up to whole Philox blocks (4 words).
 int lds_words_per_sym(int bps) { return (((bps + 7 + 31) / 32 + 1) + 3) & ~3; }
+
+// The plan's precision as a type: f(float{}) or f(double{})
+template <typename F>
+hipError_t with_prec(ofdm_plan_t p, F f) {
+    return p->prec == OFDM_F32 ? f(float{}) : f(double{});
+}
+
+// The generic fused kernel's LDS layout for this shape exceeds a CU's (launcher: kLdsOverflow).
+int lds_overflow(ofdm_plan_t p, const char* who) {
+    return fail(OFDM_E_INVALID, std::string(who) + ": the shape does not fit the LDS of a compute unit (n_fft " +
+                                    std::to_string(p->n) + ", " + (p->prec == OFDM_F32 ? "complex64" : "complex128") +
+                                    ", prefix " + std::to_string(p->cp) + ", " + std::to_string(p->L) + " taps, " +
+                                    std::to_string(p->bps) + " bits per OFDM symbol, LUT pool " +
+                                    std::to_string(p->lut_len) + ")");
+}
+
+// A launcher's answer as entry point `who`'s: the one place that translates the launchers' verdicts
+// (ofdm_launch.hpp; no HIP call can return one) -- bad arguments, each naming its reason; kNotInBuild is
+// a dispatch that reached a shape an OFDM_AB_ONLY experiment build does not instantiate -- and reports
+// any other failure as a HIP error under the entry point's name.
+int checked(const char* who, ofdm_plan_t p, hipError_t e) {
+    if (e == hipSuccess) return OFDM_OK;
+    if (e == kLdsOverflow) return lds_overflow(p, who);
+    if (e == kNoFusedForm) return fail(OFDM_E_INVALID, "ofdm_link: no fused form for this plan");
+    if (kAbOnly && e == kNotInBuild)
+        return fail(OFDM_E_INVALID, std::string(who) + ": kernel not in this build (an OFDM_AB_ONLY variant "
+                                                       "instantiates N = 1024..4096 only)");
+    return fail(OFDM_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+}
 
 }  // namespace
 
@@ -504,8 +529,6 @@ int ofdm_plan_response(ofdm_plan_t p, void* stream, double* H, double* gains) {
     return OFDM_OK;
 }
 
-#define DISPATCH(p, CALL) ((p)->prec == OFDM_F32 ? CALL(float) : CALL(double))
-
 int ofdm_fft(ofdm_plan_t p, void* stream, void* data, int64_t batch, int32_t inverse) {
     if (!p || (!data && batch > 0) || batch < 0) return fail(OFDM_E_INVALID, "bad argument to ofdm_fft");
     RowsArgs a{};
@@ -517,10 +540,9 @@ int ofdm_fft(ofdm_plan_t p, void* stream, void* data, int64_t batch, int32_t inv
     a.inverse = inverse != 0;
     a.scale = 1.0 / std::sqrt((double)p->n);
     a.tw = p->tw.p;
-#define CALL(R) launch_rows<R>(p->logn, 0, a, (hipStream_t)stream)
-    HIPCHK(DISPATCH(p, CALL));
-#undef CALL
-    return OFDM_OK;
+    return checked("ofdm_fft", p, with_prec(p, [&](auto r) {
+        return launch_rows<decltype(r)>(p->logn, 0, a, (hipStream_t)stream);
+    }));
 }
 
 int ofdm_modulate(ofdm_plan_t p, void* stream, const void* X, int64_t n_sym, void* x) {
@@ -535,10 +557,9 @@ int ofdm_modulate(ofdm_plan_t p, void* stream, const void* X, int64_t n_sym, voi
     a.zp = p->zp ? p->cp : 0;
     a.scale = 1.0 / std::sqrt((double)p->n);
     a.tw = p->tw.p;
-#define CALL(R) launch_rows<R>(p->logn, 1, a, (hipStream_t)stream)
-    HIPCHK(DISPATCH(p, CALL));
-#undef CALL
-    return OFDM_OK;
+    return checked("ofdm_modulate", p, with_prec(p, [&](auto r) {
+        return launch_rows<decltype(r)>(p->logn, 1, a, (hipStream_t)stream);
+    }));
 }
 
 int ofdm_demodulate(ofdm_plan_t p, void* stream, const void* yt, int64_t n_sym, double snr_db, void* Z) {
@@ -559,10 +580,9 @@ int ofdm_demodulate(ofdm_plan_t p, void* stream, const void* yt, int64_t n_sym, 
     a.tw = p->tw.p;
     a.eq_a = p->eq_a.p;
     a.eq_b = p->eq_b.p;
-#define CALL(R) launch_rows<R>(p->logn, 2, a, (hipStream_t)stream)
-    HIPCHK(DISPATCH(p, CALL));
-#undef CALL
-    return OFDM_OK;
+    return checked("ofdm_demodulate", p, with_prec(p, [&](auto r) {
+        return launch_rows<decltype(r)>(p->logn, 2, a, (hipStream_t)stream);
+    }));
 }
 
 int ofdm_equalize(ofdm_plan_t p, void* stream, const void* Y, int64_t n_rows, double snr_db, void* Z) {
@@ -578,10 +598,9 @@ int ofdm_equalize(ofdm_plan_t p, void* stream, const void* Y, int64_t n_rows, do
     a.gain_mean = p->gain_mean;
     a.eq_a = p->eq_a.p;
     a.eq_b = p->eq_b.p;
-#define CALL(R) launch_equalize<R>(a, (hipStream_t)stream)
-    HIPCHK(DISPATCH(p, CALL));
-#undef CALL
-    return OFDM_OK;
+    return checked("ofdm_equalize", p, with_prec(p, [&](auto r) {
+        return launch_equalize<decltype(r)>(a, (hipStream_t)stream);
+    }));
 }
 
 int ofdm_map(ofdm_plan_t p, void* stream, const uint8_t* bytes, int64_t n_bytes, int64_t n_out, void* symbols) {
@@ -601,10 +620,9 @@ int ofdm_map(ofdm_plan_t p, void* stream, const uint8_t* bytes, int64_t n_bytes,
     a.bps = p->bps;
     a.sc = (const ScInfo*)p->sc.p;
     a.axis = (const AxisInfo*)p->axis.p;
-#define CALL(R) launch_map<R>(a, (hipStream_t)stream)
-    HIPCHK(DISPATCH(p, CALL));
-#undef CALL
-    return OFDM_OK;
+    return checked("ofdm_map", p, with_prec(p, [&](auto r) {
+        return launch_map<decltype(r)>(a, (hipStream_t)stream);
+    }));
 }
 
 int ofdm_demap(ofdm_plan_t p, void* stream, const void* z, int64_t n, uint8_t* bytes) {
@@ -631,10 +649,9 @@ int ofdm_demap(ofdm_plan_t p, void* stream, const void* z, int64_t n, uint8_t* b
     a.active = (const int32_t*)p->active.p;
     a.lut64 = (const double*)p->lut64.p;
     a.wide = (const WideAxis*)p->wide.p;
-#define CALL(R) launch_demap<R>(a, (hipStream_t)stream)
-    HIPCHK(DISPATCH(p, CALL));
-#undef CALL
-    return OFDM_OK;
+    return checked("ofdm_demap", p, with_prec(p, [&](auto r) {
+        return launch_demap<decltype(r)>(a, (hipStream_t)stream);
+    }));
 }
 
 int ofdm_demap_count(ofdm_plan_t p, void* stream, const void* Z, const uint8_t* tx_bits, int64_t n_sym,
@@ -662,10 +679,9 @@ int ofdm_demap_count(ofdm_plan_t p, void* stream, const void* Z, const uint8_t* 
     a.lut_len = p->lut_len;
     a.counters = (unsigned long long*)counters;
     a.wide = (const WideAxis*)p->wide.p;
-#define CALL(R) launch_demap_count<R>(a, (hipStream_t)stream)
-    HIPCHK(DISPATCH(p, CALL));
-#undef CALL
-    return OFDM_OK;
+    return checked("ofdm_demap_count", p, with_prec(p, [&](auto r) {
+        return launch_demap_count<decltype(r)>(a, (hipStream_t)stream);
+    }));
 }
 
 int ofdm_nn_classify(void* stream, const double* lut, int32_t m, const void* z, int64_t n, int64_t* idx) {
@@ -691,38 +707,35 @@ static double* workspace(ofdm_plan_t p, void* stream) {
     return (double*)d.p;
 }
 
-static int reduce_into(ofdm_plan_t p, hipStream_t s, const double* ws, int grid, int nfields, int max_mask,
-                       double* stats) {
-    HIPCHK(launch_finalize(ws, grid, nfields, max_mask, stats, s));
-    return OFDM_OK;
-}
-
 int ofdm_channel(ofdm_plan_t p, void* stream, const void* sig, int64_t len, void* y, double* power_sum) {
     if (!p || p->L < 1) return fail(OFDM_E_INVALID, "plan has no channel taps");
     if (len < 0 || (len > 0 && (!sig || !y))) return fail(OFDM_E_INVALID, "bad argument to ofdm_channel");
     if (len == 0) return OFDM_OK;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((len + 255) / 256, kMaxGrid));
+    const int grid = clamp_grid((len + 255) / 256);
     double* ws = workspace(p, stream);
     if (!ws) return fail(OFDM_E_ALLOC, "hipMalloc failed");
     ConvArgs a{sig, y, len, p->h.p, p->L, ws};
-#define CALL(R) launch_conv<R>(a, grid, (hipStream_t)stream)
-    HIPCHK(DISPATCH(p, CALL));
-#undef CALL
-    if (power_sum) return reduce_into(p, (hipStream_t)stream, ws, grid, 1, 0, power_sum);
+    if (int rc = checked("ofdm_channel", p, with_prec(p, [&](auto r) {
+            return launch_conv<decltype(r)>(a, grid, (hipStream_t)stream);
+        })))
+        return rc;
+    if (power_sum) HIPCHK(launch_finalize(ws, grid, 1, 0, power_sum, (hipStream_t)stream));
     return OFDM_OK;
 }
 
 int ofdm_power(ofdm_plan_t p, void* stream, const void* y, int64_t len, double* power_sum) {
     if (!p || len < 0 || (len > 0 && !y) || !power_sum) return fail(OFDM_E_INVALID, "bad argument to ofdm_power");
     if (len == 0) return OFDM_OK;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((len + 255) / 256, kMaxGrid));
+    const int grid = clamp_grid((len + 255) / 256);
     double* ws = workspace(p, stream);
     if (!ws) return fail(OFDM_E_ALLOC, "hipMalloc failed");
     PowerArgs a{y, len, ws};
-#define CALL(R) launch_power<R>(a, grid, (hipStream_t)stream)
-    HIPCHK(DISPATCH(p, CALL));
-#undef CALL
-    return reduce_into(p, (hipStream_t)stream, ws, grid, 1, 0, power_sum);
+    if (int rc = checked("ofdm_power", p, with_prec(p, [&](auto r) {
+            return launch_power<decltype(r)>(a, grid, (hipStream_t)stream);
+        })))
+        return rc;
+    HIPCHK(launch_finalize(ws, grid, 1, 0, power_sum, (hipStream_t)stream));
+    return OFDM_OK;
 }
 
 int ofdm_awgn(ofdm_plan_t p, void* stream, void* y, int64_t len, const double* nr, const double* ni,
@@ -730,10 +743,9 @@ int ofdm_awgn(ofdm_plan_t p, void* stream, void* y, int64_t len, const double* n
     if (!p || len < 0 || (len > 0 && (!y || !nr || !ni || !power_sum)))
         return fail(OFDM_E_INVALID, "bad argument to ofdm_awgn");
     AwgnArgs a{y, len, nr, ni, power_sum, std::pow(10.0, snr_db / 10.0)};
-#define CALL(R) launch_awgn<R>(a, (hipStream_t)stream)
-    HIPCHK(DISPATCH(p, CALL));
-#undef CALL
-    return OFDM_OK;
+    return checked("ofdm_awgn", p, with_prec(p, [&](auto r) {
+        return launch_awgn<decltype(r)>(a, (hipStream_t)stream);
+    }));
 }
 
 // Throughput mode (bits == NULL: Philox stream version 3) gives each element one byte of its lane
@@ -744,15 +756,6 @@ static int stream_bits_ok(ofdm_plan_t p, const uint8_t* bits, const char* who) {
     return fail(OFDM_E_INVALID, std::string(who) + ": the throughput (Philox) bit stream carries at most 8 bits per "
                                     "subcarrier and this plan has up to " + std::to_string(p->max_bits) +
                                     "; pass the tx bits (reference-stream mode)");
-}
-
-// The generic fused kernel's LDS layout for this shape exceeds a CU's (launcher: kLdsOverflow).
-static int lds_overflow(ofdm_plan_t p, const char* who) {
-    return fail(OFDM_E_INVALID, std::string(who) + ": the shape does not fit the LDS of a compute unit (n_fft " +
-                                    std::to_string(p->n) + ", " + (p->prec == OFDM_F32 ? "complex64" : "complex128") +
-                                    ", prefix " + std::to_string(p->cp) + ", " + std::to_string(p->L) + " taps, " +
-                                    std::to_string(p->bps) + " bits per OFDM symbol, LUT pool " +
-                                    std::to_string(p->lut_len) + ")");
 }
 
 static void fill_common(ofdm_plan_t p, TxRxCommon& c, const uint8_t* bits, uint64_t seed, int64_t sym0,
@@ -838,13 +841,13 @@ static int tx_call(const char* who, ofdm_plan_t p, void* stream, const uint8_t* 
     a.slot = tx_slot(p->logn, p->cp, p->L);
     a.flags = OFDM_ENV_FLAGS("OFDM_ABLATE_TX");
     int grid = 0;  // chosen by the launcher with the kernel (<= kMaxGrid partial records)
-#define CALL(R) (clip ? launch_tx_clip<R>(p->logn, a, clip->a2, clip->a2 * p->h0_norm2,                           \
-                                         (unsigned long long*)clip->counters, &grid, (hipStream_t)stream) \
-                      : launch_tx<R>(p->logn, a, &grid, (hipStream_t)stream))
-    const hipError_t launch_result = DISPATCH(p, CALL);
-#undef CALL
-    if (launch_result == kLdsOverflow) return lds_overflow(p, who);
-    HIPCHK(launch_result);
+    if (int rc = checked(who, p, with_prec(p, [&](auto r) {
+            using R = decltype(r);
+            return clip ? launch_tx_clip<R>(p->logn, a, clip->a2, clip->a2 * p->h0_norm2,
+                                            (unsigned long long*)clip->counters, &grid, (hipStream_t)stream)
+                        : launch_tx<R>(p->logn, a, &grid, (hipStream_t)stream);
+        })))
+        return rc;
     HIPCHK(launch_finalize_tx(a.partials, grid, (double*)stats, (hipStream_t)stream));
     return OFDM_OK;
 }
@@ -907,14 +910,10 @@ static int rx_call(const char* who, ofdm_plan_t p, void* stream, const void* y, 
     a.flags = OFDM_ENV_FLAGS("OFDM_ABLATE_RX");
     a.wide = p->wide_plan ? (const WideAxis*)p->wide.p : nullptr;  // an order above 256: the wide slicer
     a.profile = profile;
-    int grid = 0;
-#define CALL(R) (profile ? launch_rx_prof<R>(p->logn, a, &grid, (hipStream_t)stream) \
-                         : launch_rx<R>(p->logn, a, &grid, (hipStream_t)stream))
-    const hipError_t launch_result = DISPATCH(p, CALL);
-#undef CALL
-    if (launch_result == kLdsOverflow) return lds_overflow(p, who);
-    HIPCHK(launch_result);
-    return OFDM_OK;
+    return checked(who, p, with_prec(p, [&](auto r) {
+        using R = decltype(r);
+        return profile ? launch_rx_prof<R>(p->logn, a, (hipStream_t)stream) : launch_rx<R>(p->logn, a, (hipStream_t)stream);
+    }));
 }
 
 int ofdm_rx(ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni, uint64_t seed,
@@ -956,13 +955,9 @@ int ofdm_rx_sweep(ofdm_plan_t p, void* stream, const void* y, uint64_t seed, con
     a.n_snr = n_snr;
     for (int k = 0; k < n_snr; ++k) a.snr_lin[k] = std::pow(10.0, snr_db[k] / 10.0);  // (as ofdm_rx)
     a.r.snr_lin = a.snr_lin[0];
-    int grid = 0;
-#define CALL(R) launch_rx_sweep<R>(p->logn, a, &grid, (hipStream_t)stream)
-    const hipError_t launch_result = DISPATCH(p, CALL);
-#undef CALL
-    if (launch_result == kLdsOverflow) return lds_overflow(p, "ofdm_rx_sweep");
-    HIPCHK(launch_result);
-    return OFDM_OK;
+    return checked("ofdm_rx_sweep", p, with_prec(p, [&](auto r) {
+        return launch_rx_sweep<decltype(r)>(p->logn, a, (hipStream_t)stream);
+    }));
 }
 
 // ofdm_link, ofdm_link_sparse, ofdm_link_nscreen and ofdm_link_screen (screen: the kernel's, kLinkScreen*;
@@ -1001,12 +996,7 @@ static int link_call(int screen, ofdm_plan_t p, void* stream, uint64_t seed, con
     a.h = p->h.p;
     a.mode = mode;
     a.screen_counts = (unsigned long long*)screen_counts;
-    int grid = 0;
-    const hipError_t launch_result = launch_link<double>(p->logn, p->L, a, screen, &grid, (hipStream_t)stream);
-    if (launch_result == hipErrorInvalidValue) return fail(OFDM_E_INVALID, "ofdm_link: no fused form for this plan");
-    if (launch_result == kLdsOverflow) return lds_overflow(p, "ofdm_link");
-    HIPCHK(launch_result);
-    return OFDM_OK;
+    return checked("ofdm_link", p, launch_link<double>(p->logn, p->L, a, screen, (hipStream_t)stream));
 }
 
 // the mode of the entry points that take one (name: the entry point's, for the message)
@@ -1083,12 +1073,10 @@ int ofdm_papr(ofdm_plan_t p, void* stream, const uint8_t* bits, uint64_t seed, i
         a.hist = (unsigned long long*)hist;
         a.sym_out = (sym_out && sym_keep > done) ? sym_out + 2 * done : nullptr;
         a.sym_keep = a.sym_out ? sym_keep - done : 0;
-        int grid = 0;
-#define CALL(R) launch_papr<R>(p->logn, a, &grid, (hipStream_t)stream)
-        const hipError_t launch_result = DISPATCH(p, CALL);
-#undef CALL
-        if (launch_result == kLdsOverflow) return lds_overflow(p, "ofdm_papr");
-        HIPCHK(launch_result);
+        if (int rc = checked("ofdm_papr", p, with_prec(p, [&](auto r) {
+                return launch_papr<decltype(r)>(p->logn, a, (hipStream_t)stream);
+            })))
+            return rc;
     }
     return OFDM_OK;
 }

@@ -2,5 +2,5 @@
 #include "ofdm_link_inst.hpp"
 
 namespace ofdm {
-template hipError_t launch_link<double>(int, int, const LinkArgs&, int, int*, hipStream_t);
+template hipError_t launch_link<double>(int, int, const LinkArgs&, int, hipStream_t);
 }  // namespace ofdm

@@ -44,11 +44,29 @@ constexpr hipError_t kOutOfRange = kNotInBuild;
 constexpr hipError_t kOutOfRange = hipErrorInvalidValue;
 #endif
 
-constexpr int kFastMinLogN = 6;  // throughput specialisations for N >= 64
-
-static inline int clamp_grid(int64_t want) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(want, kMaxGrid));
+// log2 N as a compile-time constant: f(std::integral_constant<int, L>) for the build's cases -- the
+// one switch on logn of every launcher
+template <typename F>
+static hipError_t with_logn(int logn, F f) {
+#define OFDM_LOGN_CASE(L) \
+    case L:               \
+        return f(std::integral_constant<int, L>{});
+    switch (logn) {
+        OFDM_LOGN_CASES(OFDM_LOGN_CASE)
+        default:
+            return kOutOfRange;
+    }
+#undef OFDM_LOGN_CASE
 }
+// c.eq as a compile-time constant: f(std::integral_constant<int, OFDM_EQ_*>)
+template <typename F>
+static hipError_t with_eq(int eq, F f) {
+    if (eq == OFDM_EQ_NONE) return f(std::integral_constant<int, OFDM_EQ_NONE>{});
+    if (eq == OFDM_EQ_ZF) return f(std::integral_constant<int, OFDM_EQ_ZF>{});
+    return f(std::integral_constant<int, OFDM_EQ_MMSE>{});
+}
+
+constexpr int kFastMinLogN = 6;  // throughput specialisations for N >= 64
 
 template <typename R, int LOGN, int MODE>
 static hipError_t rows_one(const RowsArgs& a, hipStream_t s) {
@@ -66,17 +84,12 @@ static hipError_t rows_one(const RowsArgs& a, hipStream_t s) {
 template <typename R>
 hipError_t launch_rows(int logn, int mode, const RowsArgs& a, hipStream_t s) {
     if (a.n_rows <= 0) return hipSuccess;
-#define OFDM_ROWS_CASE(L)                                   \
-    case L:                                                 \
-        if (mode == 0) return rows_one<R, L, 0>(a, s);      \
-        if (mode == 1) return rows_one<R, L, 1>(a, s);      \
+    return with_logn(logn, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        if (mode == 0) return rows_one<R, L, 0>(a, s);
+        if (mode == 1) return rows_one<R, L, 1>(a, s);
         return rows_one<R, L, 2>(a, s);
-    switch (logn) {
-        OFDM_LOGN_CASES(OFDM_ROWS_CASE)
-        default:
-            return kOutOfRange;
-    }
-#undef OFDM_ROWS_CASE
+    });
 }
 
 // The elementwise kernels: `grid` workgroups of kBlock threads, no dynamic LDS (per_block: one
@@ -161,15 +174,21 @@ static inline int tx_chunk(int64_t n_sym, int max_chunk, int spb, int resident) 
     return best;
 }
 
-// OFDM_GRID_RESIDENT k > 0 (A/B): the fused receiver's grid capped at k x the workgroups resident at
-// once, so each workgroup stages its tables once and loops over its share of the symbols (the
-// transmitter lost 4-8 % that way: profiles/r05h_ab_grid_resident.txt)
-#ifndef OFDM_GRID_RESIDENT
-#define OFDM_GRID_RESIDENT 0
-#endif
-static inline int fused_grid(int64_t want, int resident) {
-    if (OFDM_GRID_RESIDENT > 0 && resident > 0) want = std::min<int64_t>(want, (int64_t)OFDM_GRID_RESIDENT * resident);
-    return clamp_grid(want);
+// The tail of every fused transmitter launch (k_tx and its CLIP instantiations; tail: the kernel
+// arguments behind TxArgs), after the launcher has sized the layout: `sm` bytes of dynamic LDS opted in,
+// the multipath chunk fitted to whole rounds of the resident workgroups (tx_chunk), an uncapped grid of
+// one workgroup per SPB symbol groups -- capping it at the resident workgroups, as rx_go does, cost the
+// transmitter 4-8 % (profiles/r05h_ab_grid_resident.txt) -- returned in *grid, and the launch.
+template <int BLK, int SPB, typename K, typename... T>
+static hipError_t tx_go(K fn, size_t sm, TxArgs& a, int* grid, hipStream_t s, const T&... tail) {
+    const hipError_t e = set_smem(fn, sm);
+    if (e != hipSuccess) return e;
+    const int resident = resident_blocks(fn, BLK, sm);
+    if (a.chunk > 1) a.chunk = tx_chunk(a.c.n_sym, a.chunk, SPB, resident);
+    const int64_t groups = (a.c.n_sym + a.chunk - 1) / a.chunk;
+    *grid = clamp_grid((groups + SPB - 1) / SPB);
+    hipLaunchKernelGGL(fn, dim3(*grid), dim3(BLK), sm, s, a, tail...);
+    return hipGetLastError();
 }
 
 // WIDE: the generic kernel's instantiation for a plan with an order above 256 (a.wide set)
@@ -189,15 +208,7 @@ static hipError_t tx_launch(const TxArgs& a0, int* grid, hipStream_t s) {
         // the generic kernel is the last resort: a shape it cannot hold is refused, not launched
         if (sm + tx_static_lds<R, FB, LT>() > kLdsPerCu) return kLdsOverflow;
     }
-    auto fn = k_tx<R, LOGN, FB, LT, ZPW, REF, WIDE>;
-    hipError_t e = set_smem(fn, sm);
-    if (e != hipSuccess) return e;
-    const int resident = resident_blocks(fn, BLK, sm);
-    if (a.chunk > 1) a.chunk = tx_chunk(a.c.n_sym, a.chunk, Geo<LOGN, BLK>::SPB, resident);
-    const int64_t groups = (a.c.n_sym + a.chunk - 1) / a.chunk;
-    *grid = clamp_grid((groups + Geo<LOGN, BLK>::SPB - 1) / Geo<LOGN, BLK>::SPB);
-    hipLaunchKernelGGL(fn, dim3(*grid), dim3(BLK), sm, s, a);
-    return hipGetLastError();
+    return tx_go<BLK, Geo<LOGN, BLK>::SPB>(k_tx<R, LOGN, FB, LT, ZPW, REF, WIDE>, sm, a, grid, s);
 }
 
 // throughput TX by channel length: flat / window FIR (<= 4 or <= 8 taps) / run-time taps (REF, see
@@ -272,14 +283,6 @@ static bool bench_shape(const TxRxCommon& c) {
 template <typename R, int LOGN>
 static bool ref_shape(const TxRxCommon& c) { return c.bits != nullptr && bench_shape<R, LOGN>(c); }
 
-// c.eq as a compile-time constant: f(std::integral_constant<int, OFDM_EQ_*>)
-template <typename F>
-static hipError_t with_eq(int eq, F f) {
-    if (eq == OFDM_EQ_NONE) return f(std::integral_constant<int, OFDM_EQ_NONE>{});
-    if (eq == OFDM_EQ_ZF) return f(std::integral_constant<int, OFDM_EQ_ZF>{});
-    return f(std::integral_constant<int, OFDM_EQ_MMSE>{});
-}
-
 // Throughput configuration (Philox bits, N >= 64): fixed_fast -> the kernel specialised on the bits
 // per subcarrier; adaptive_fast -> the adaptive throughput kernel (FB = 1); anything else -> the
 // generic kernel.
@@ -308,79 +311,69 @@ static hipError_t tx_one(const TxArgs& a, int* grid, hipStream_t s) {
 
 template <typename R>
 hipError_t launch_tx(int logn, const TxArgs& a, int* grid, hipStream_t s) {
-#define OFDM_TX_CASE(L) \
-    case L:             \
-        return tx_one<R, L>(a, grid, s);
-    switch (logn) {
-        OFDM_LOGN_CASES(OFDM_TX_CASE)
-        default:
-            return kOutOfRange;
-    }
-#undef OFDM_TX_CASE
+    return with_logn(logn, [&](auto l) { return tx_one<R, decltype(l)::value>(a, grid, s); });
 }
 
-// The tail of every fused receiver launch (k_rx, k_rx_prof, k_rx_sweep), after the launcher has sized
-// the layout: `sm` bytes of dynamic LDS opted in, a grid of ceil(n_sym / SPB) workgroups capped at
-// `rounds` rounds of the workgroups resident at once, each then looping over its share of the symbols
-// (rounds = 0, or a runtime that cannot say: uncapped up to kMaxGrid, or OFDM_GRID_RESIDENT's A/B cap),
-// and the launch.
+// The tail of every fused receiver launch (k_rx, k_rx_prof, k_rx_sweep, k_link, k_papr), after the
+// launcher has sized the layout: `sm` bytes of dynamic LDS opted in, a grid of ceil(n_sym / SPB)
+// workgroups capped at `rounds` rounds of the workgroups resident at once, each then looping over its
+// share of the symbols (rounds = 0, or a runtime that cannot say: uncapped up to kMaxGrid), and the launch.
 template <int BLK, int SPB, typename K, typename A>
-static hipError_t rx_go(K fn, size_t sm, int rounds, int64_t n_sym, const A& a, int* grid, hipStream_t s) {
+static hipError_t rx_go(K fn, size_t sm, int rounds, int64_t n_sym, const A& a, hipStream_t s) {
     const hipError_t e = set_smem(fn, sm);
     if (e != hipSuccess) return e;
-    const int64_t want = (n_sym + SPB - 1) / SPB;
+    int64_t want = (n_sym + SPB - 1) / SPB;
     const int res = rounds > 0 ? resident_blocks(fn, BLK, sm) : 0;
-    *grid = res > 0 ? clamp_grid(std::min<int64_t>(want, (int64_t)rounds * res))
-                    : fused_grid(want, OFDM_GRID_RESIDENT > 0 ? resident_blocks(fn, BLK, sm) : 0);
-    hipLaunchKernelGGL(fn, dim3(*grid), dim3(BLK), sm, s, a);
+    if (res > 0) want = std::min<int64_t>(want, (int64_t)rounds * res);
+    hipLaunchKernelGGL(fn, dim3(clamp_grid(want)), dim3(BLK), sm, s, a);
     return hipGetLastError();
 }
 
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
-static hipError_t rx_launch(const RxArgs& a, int* grid, hipStream_t s) {
+static hipError_t rx_launch(const RxArgs& a, hipStream_t s) {
     constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV>();
     if ((a.wide != nullptr) != WIDE) return hipErrorInvalidValue;  // (as tx_launch)
     CarveSize lds;
     rx_carve<R, LOGN, EQ, FB, MV>(lds, a.c.words_per_sym, rx_tts<R, LOGN, FB>(a.c.scm), WIDE ? a.c.n_axis : 0);
     if (lds.bytes + rx_static_lds<R, FB>() > kLdsPerCu) {  // (as tx_launch)
-        if constexpr (FB > 0) return rx_launch<R, LOGN, -1, 0, true>(a, grid, s);
+        if constexpr (FB > 0) return rx_launch<R, LOGN, -1, 0, true>(a, s);
         else return kLdsOverflow;
     }
     return rx_go<BLK, Geo<LOGN, BLK>::SPB>(k_rx<R, LOGN, EQ, FB, MV, REF, WIDE>, lds.bytes,
-                                           rx_grid_rounds<R, FB, LOGN>(), a.c.n_sym, a, grid, s);
+                                           rx_grid_rounds<R, FB, LOGN>(), a.c.n_sym, a, s);
 }
 
 // MV: the run-time modem variants (SC-OFDM, zero padding) compiled in.  complex128 builds them as
 // separate kernels: compiled into the cyclic-prefix OFDM kernels of the bench, their second
 // transform and guard overlap-add spilled the config (b) receiver (~70 dwords at 128 VGPRs)
 template <typename R, int LOGN, int FB, bool MV = true, bool REF = false>
-static hipError_t rx_eq(const RxArgs& a, int* grid, hipStream_t s) {
-    return with_eq(a.c.eq, [&](auto eq) { return rx_launch<R, LOGN, decltype(eq)::value, FB, MV, REF>(a, grid, s); });
+static hipError_t rx_eq(const RxArgs& a, hipStream_t s) {
+    return with_eq(a.c.eq, [&](auto eq) { return rx_launch<R, LOGN, decltype(eq)::value, FB, MV, REF>(a, s); });
 }
 
 // Throughput configuration (Philox bits and noise, no received-symbol tap; N >= 64): fixed_fast ->
 // the kernel specialised on bits and equaliser; adaptive_fast -> the adaptive one; anything else ->
 // the generic kernel.
 template <typename R, int LOGN>
-static hipError_t rx_one(const RxArgs& a, int* grid, hipStream_t s) {
+static hipError_t rx_one(const RxArgs& a, hipStream_t s) {
     if constexpr (ref_fb<R, LOGN>() > 0) {
         // reference streams on a bench shape (see ref_shape): the REF receiver needs the caller's
         // normals and no received-symbol tap
         // (MV: as the timed kernels -- compiled out of the fixed-QAM ones, and in the adaptive
         // kernel's instantiation, where FB = 1 forces SC-OFDM and zero padding off)
         if (ref_shape<R, LOGN>(a.c) && a.nr != nullptr && a.z_out == nullptr)
-            return rx_eq<R, LOGN, ref_fb<R, LOGN>(), ref_fb<R, LOGN>() == 1, true>(a, grid, s);
+            return rx_eq<R, LOGN, ref_fb<R, LOGN>(), ref_fb<R, LOGN>() == 1, true>(a, s);
     }
     if constexpr (LOGN >= kFastMinLogN) {
         const bool streams = philox_streams(a);
-        if (streams && adaptive_fast(a.c)) return rx_eq<R, LOGN, 1>(a, grid, s);
+        if (streams && adaptive_fast(a.c)) return rx_eq<R, LOGN, 1>(a, s);
         if (streams && fixed_fast(a.c)) {
 #define OFDM_RX_FB(F)                                                                      \
     case F:                                                                                \
         if constexpr (sizeof(R) == 8) { /* the modem variants in kernels of their own: rx_eq */ \
-            if (!a.c.scm && !a.c.zpad) return rx_eq<R, LOGN, F, false>(a, grid, s);        \
+            if (!a.c.scm && !a.c.zpad) return rx_eq<R, LOGN, F, false>(a, s);        \
         }                                                                                  \
-        return rx_eq<R, LOGN, F, true>(a, grid, s);
+        return rx_eq<R, LOGN, F, true>(a, s);
             switch (a.c.b) {
                 OFDM_FB_CASES(OFDM_RX_FB)
                 default: break;
@@ -388,21 +381,13 @@ static hipError_t rx_one(const RxArgs& a, int* grid, hipStream_t s) {
 #undef OFDM_RX_FB
         }
     }
-    if (a.wide != nullptr) return rx_launch<R, LOGN, -1, 0, true, false, true>(a, grid, s);  // (as tx_one)
-    return rx_launch<R, LOGN, -1, 0, true>(a, grid, s);
+    if (a.wide != nullptr) return rx_launch<R, LOGN, -1, 0, true, false, true>(a, s);  // (as tx_one)
+    return rx_launch<R, LOGN, -1, 0, true>(a, s);
 }
 
 template <typename R>
-hipError_t launch_rx(int logn, const RxArgs& a, int* grid, hipStream_t s) {
-#define OFDM_RX_CASE(L) \
-    case L:             \
-        return rx_one<R, L>(a, grid, s);
-    switch (logn) {
-        OFDM_LOGN_CASES(OFDM_RX_CASE)
-        default:
-            return kOutOfRange;
-    }
-#undef OFDM_RX_CASE
+hipError_t launch_rx(int logn, const RxArgs& a, hipStream_t s) {
+    return with_logn(logn, [&](auto l) { return rx_one<R, decltype(l)::value>(a, s); });
 }
 
 // The launchers are instantiated in three groups so the complex64 kernels -- the bulk of
@@ -417,7 +402,7 @@ hipError_t launch_rx(int logn, const RxArgs& a, int* grid, hipStream_t s) {
     template hipError_t launch_power<R>(const PowerArgs&, int, hipStream_t);        \
     template hipError_t launch_awgn<R>(const AwgnArgs&, hipStream_t);
 #define OFDM_INSTANTIATE_TX(R) template hipError_t launch_tx<R>(int, const TxArgs&, int*, hipStream_t);
-#define OFDM_INSTANTIATE_RX(R) template hipError_t launch_rx<R>(int, const RxArgs&, int*, hipStream_t);
+#define OFDM_INSTANTIATE_RX(R) template hipError_t launch_rx<R>(int, const RxArgs&, hipStream_t);
 #define OFDM_INSTANTIATE(R) OFDM_INSTANTIATE_OPS(R) OFDM_INSTANTIATE_TX(R) OFDM_INSTANTIATE_RX(R)
 
 }  // namespace ofdm

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "ofdm_device.hpp"
 #include "ofdm_hip.h"
 
@@ -20,6 +22,9 @@ namespace ofdm {
 __host__ __device__ constexpr int ablation_flags(int f) { return OFDM_ABLATION ? f : 0; }
 
 constexpr int kMaxGrid = 4096;  // partial-sum workspace rows
+static inline int clamp_grid(int64_t want) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(want, kMaxGrid));
+}
 // fused TX partials per workgroup: sum |y|^2 as fixed-point limbs (2 x u64), sum |x|^2, max |x|^2
 constexpr int kTxFields = 4;
 constexpr int kMaxTaps = 32;
@@ -235,18 +240,23 @@ constexpr int tx_slot(int logn, int cp, int L) {
     return padded_row(1 << logn) > ext ? padded_row(1 << logn) : ext;
 }
 
-// A launcher's answer for a shape its build does not instantiate (OFDM_AB_ONLY experiment builds:
-// N = 1024..4096 only); the ABI reports it as OFDM_E_INVALID "kernel not in this build".  Product
-// builds instantiate every shape a plan accepts and never return it.
+// The launchers' own verdicts: values of hipError_t's range that are no enumerator of it (the largest
+// is 1054), so no HIP call can return one.  ofdm_abi.hip's checked() is the one place that translates
+// them; nothing was launched when a launcher answers one.
+//   kNotInBuild: a shape this build does not instantiate (OFDM_AB_ONLY experiment builds: N = 1024..4096
+//     only) -- OFDM_E_INVALID "kernel not in this build".  Product builds instantiate every shape a plan
+//     accepts and never return it.
+//   kLdsOverflow: a fused launcher's shape whose LDS layout does not fit a CU (kLdsPerCu) --
+//     OFDM_E_INVALID naming the shape.
+//   kNoFusedForm: launch_link's plan or arguments have no fused form -- OFDM_E_INVALID.
 #ifdef OFDM_AB_ONLY
 constexpr bool kAbOnly = true;
 #else
 constexpr bool kAbOnly = false;
 #endif
-constexpr hipError_t kNotInBuild = hipErrorNotSupported;  // (only ever meant so when kAbOnly)
-// A fused launcher's answer for a shape whose LDS layout does not fit a CU (kLdsPerCu): nothing was
-// launched; the ABI reports it as OFDM_E_INVALID naming the shape.
-constexpr hipError_t kLdsOverflow = hipErrorLaunchOutOfResources;
+constexpr hipError_t kNotInBuild = static_cast<hipError_t>(2001);  // (only ever answered when kAbOnly)
+constexpr hipError_t kLdsOverflow = static_cast<hipError_t>(2002);
+constexpr hipError_t kNoFusedForm = static_cast<hipError_t>(2003);
 
 // ---- launchers (instantiated for float and double in ofdm_kernels_f{32,64}.hip)
 template <typename R>
@@ -265,28 +275,29 @@ template <typename R>
 hipError_t launch_power(const PowerArgs& a, int grid, hipStream_t s);
 template <typename R>
 hipError_t launch_awgn(const AwgnArgs& a, hipStream_t s);
-// the fused launchers pick the kernel (and its workgroup size) and return the grid used
+// the fused launchers pick the kernel, its workgroup size and its grid; the two transmitters return
+// the grid used (launch_finalize_tx reduces that many partial records)
 template <typename R>
 hipError_t launch_tx(int logn, const TxArgs& a, int* grid, hipStream_t s);
 template <typename R>
-hipError_t launch_rx(int logn, const RxArgs& a, int* grid, hipStream_t s);
+hipError_t launch_rx(int logn, const RxArgs& a, hipStream_t s);
 // the receiver with the per-subcarrier profile (a.profile set; ofdm_prof_inst.hpp)
 template <typename R>
-hipError_t launch_rx_prof(int logn, const RxArgs& a, int* grid, hipStream_t s);
+hipError_t launch_rx_prof(int logn, const RxArgs& a, hipStream_t s);
 
 // the one-pass SNR sweep receiver (ofdm_sweep_inst.hpp)
 template <typename R>
-hipError_t launch_rx_sweep(int logn, const RxSweepArgs& a, int* grid, hipStream_t s);
+hipError_t launch_rx_sweep(int logn, const RxSweepArgs& a, hipStream_t s);
 
 // the fused link kernel (ofdm_link_inst.hpp; complex128 only); L: the plan's channel taps.
-// hipErrorInvalidValue: the plan or the arguments have no fused form, nothing was launched
+// kNoFusedForm: the plan or the arguments have no fused form, nothing was launched
 template <typename R>
-hipError_t launch_link(int logn, int L, const LinkArgs& a, int screen, int* grid, hipStream_t s);
+hipError_t launch_link(int logn, int L, const LinkArgs& a, int screen, hipStream_t s);
 
 // the per-symbol PAPR histogram (ofdm_papr_inst.hpp); a plan with an order above 256 is refused by
 // the ABI before it
 template <typename R>
-hipError_t launch_papr(int logn, const PaprArgs& a, int* grid, hipStream_t s);
+hipError_t launch_papr(int logn, const PaprArgs& a, hipStream_t s);
 
 // the clipped transmitter (ofdm_txclip_inst.hpp); a2: A2, a2_h0: A2 |h0|^2 (the flat throughput form's
 // threshold, computed on the host in double); a wide plan is refused by the ABI before it

@@ -544,7 +544,7 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
     }
 }
 
-// What has a fused form (the one definition: launch_link answers hipErrorInvalidValue for anything
+// What has a fused form (the one definition: launch_link answers kNoFusedForm for anything
 // else and ofdm_link names the reason): a complex128 fixed-QAM bench shape (ref_fb > 1) at a symbol per
 // wave with its per-pass twiddles in LDS, a flat channel, no equaliser, Philox streams.
 template <typename R, int LOGN>
@@ -563,9 +563,9 @@ static bool link_shape(const LinkArgs& a, int L) {
 }
 
 template <typename R, int LOGN>
-static hipError_t link_one(const LinkArgs& a, int L, int screen, int* grid, hipStream_t s) {
+static hipError_t link_one(const LinkArgs& a, int L, int screen, hipStream_t s) {
     if constexpr (link_fb<R, LOGN>() > 0) {
-        if (!link_shape<R, LOGN>(a, L)) return hipErrorInvalidValue;
+        if (!link_shape<R, LOGN>(a, L)) return kNoFusedForm;
         constexpr int FB = link_fb<R, LOGN>();
         constexpr int BLK = OFDM_LINK_BLOCK;
         static_assert(Geo<LOGN, BLK>::SPB * Geo<LOGN, BLK>::TPS == BLK, "whole symbols per workgroup");
@@ -576,7 +576,7 @@ static hipError_t link_one(const LinkArgs& a, int L, int screen, int* grid, hipS
             link_carve<R, LOGN, SCREEN, FB>(lds);
             if (lds.bytes + link_static_lds<R, FB>() > kLdsPerCu) return kLdsOverflow;
             return rx_go<BLK, Geo<LOGN, BLK>::SPB>(k_link<R, LOGN, FB, SCREEN>, lds.bytes,
-                                                   rx_grid_rounds<R, FB, LOGN>(), a.r.c.n_sym, a, grid, s);
+                                                   rx_grid_rounds<R, FB, LOGN>(), a.r.c.n_sym, a, s);
         };
         // screen off: the unscreened kernel itself, not the screened one with its decision forced
         switch (a.mode == OFDM_LINK_SCREEN_OFF ? kLinkScreenNone : screen) {
@@ -586,22 +586,14 @@ static hipError_t link_one(const LinkArgs& a, int L, int screen, int* grid, hipS
             default: return go(std::integral_constant<int, kLinkScreenTwo>{});
         }
     } else {
-        return hipErrorInvalidValue;
+        return kNoFusedForm;
     }
 }
 
-// hipErrorInvalidValue: no fused form for this plan or these arguments (nothing launched)
+// kNoFusedForm: no fused form for this plan or these arguments (nothing launched)
 template <typename R>
-hipError_t launch_link(int logn, int L, const LinkArgs& a, int screen, int* grid, hipStream_t s) {
-#define OFDM_LINK_CASE(LG) \
-    case LG:               \
-        return link_one<R, LG>(a, L, screen, grid, s);
-    switch (logn) {
-        OFDM_LOGN_CASES(OFDM_LINK_CASE)
-        default:
-            return kOutOfRange;
-    }
-#undef OFDM_LINK_CASE
+hipError_t launch_link(int logn, int L, const LinkArgs& a, int screen, hipStream_t s) {
+    return with_logn(logn, [&](auto l) { return link_one<R, decltype(l)::value>(a, L, screen, s); });
 }
 
 }  // namespace ofdm

@@ -238,7 +238,7 @@ static bool papr_fast_shape(const TxRxCommon& c) {
 }
 
 template <typename R, int LOGN, int FB>
-static hipError_t papr_launch(const PaprArgs& a, int* grid, hipStream_t s) {
+static hipError_t papr_launch(const PaprArgs& a, hipStream_t s) {
     constexpr int BLK = papr_block<FB>();
     using G = Geo<LOGN, BLK>;
     static_assert(G::SPB * G::TPS == BLK, "whole symbols per workgroup");
@@ -246,36 +246,28 @@ static hipError_t papr_launch(const PaprArgs& a, int* grid, hipStream_t s) {
     papr_carve<R, LOGN, FB>(lds, a.c.lut_len, a.c.words_per_sym);
     if (lds.bytes + papr_static_lds<R, FB>() > kLdsPerCu) {
         // (a layout that does not fit: the generic form, which is the last resort)
-        if constexpr (FB > 0) return papr_launch<R, LOGN, 0>(a, grid, s);
+        if constexpr (FB > 0) return papr_launch<R, LOGN, 0>(a, s);
         else return kLdsOverflow;
     }
     // every workgroup stages the edges and ends with an atomic per non-empty bin: two rounds of the
     // resident workgroups (as the profile's and the sweep's launchers)
-    return rx_go<BLK, G::SPB>(k_papr<R, LOGN, FB>, lds.bytes, 2, a.c.n_sym, a, grid, s);
+    return rx_go<BLK, G::SPB>(k_papr<R, LOGN, FB>, lds.bytes, 2, a.c.n_sym, a, s);
 }
 
 template <typename R, int LOGN>
-static hipError_t papr_one(const PaprArgs& a, int* grid, hipStream_t s) {
+static hipError_t papr_one(const PaprArgs& a, hipStream_t s) {
     if constexpr (papr_fb<R, LOGN>() > 0) {
-        if (papr_fast_shape<R, LOGN>(a.c)) return papr_launch<R, LOGN, papr_fb<R, LOGN>()>(a, grid, s);
+        if (papr_fast_shape<R, LOGN>(a.c)) return papr_launch<R, LOGN, papr_fb<R, LOGN>()>(a, s);
     }
-    return papr_launch<R, LOGN, 0>(a, grid, s);
+    return papr_launch<R, LOGN, 0>(a, s);
 }
 
 template <typename R>
-hipError_t launch_papr(int logn, const PaprArgs& a, int* grid, hipStream_t s) {
+hipError_t launch_papr(int logn, const PaprArgs& a, hipStream_t s) {
     if (a.n_edges < 1 || a.n_edges > OFDM_MAX_PAPR_EDGES || a.hist == nullptr) return hipErrorInvalidValue;
-#define OFDM_PAPR_CASE(L) \
-    case L:               \
-        return papr_one<R, L>(a, grid, s);
-    switch (logn) {
-        OFDM_LOGN_CASES(OFDM_PAPR_CASE)
-        default:
-            return kOutOfRange;
-    }
-#undef OFDM_PAPR_CASE
+    return with_logn(logn, [&](auto l) { return papr_one<R, decltype(l)::value>(a, s); });
 }
 
-#define OFDM_INSTANTIATE_PAPR(R) template hipError_t launch_papr<R>(int, const PaprArgs&, int*, hipStream_t);
+#define OFDM_INSTANTIATE_PAPR(R) template hipError_t launch_papr<R>(int, const PaprArgs&, hipStream_t);
 
 }  // namespace ofdm

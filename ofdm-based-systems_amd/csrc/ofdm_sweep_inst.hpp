@@ -12,7 +12,7 @@ namespace ofdm {
 // FB = 0): complex64, SC-OFDM, zero padding, PSK, N < 64, adaptive plans (one plan for every point:
 // adaptive loading re-derived per SNR is a different plan per point and not a sweep).
 template <typename R, int LOGN, int EQ, int FB>
-static hipError_t rx_sweep_launch(const RxSweepArgs& a, int* grid, hipStream_t s) {
+static hipError_t rx_sweep_launch(const RxSweepArgs& a, hipStream_t s) {
     constexpr bool MV = FB == 0;  // (the generic kernel as rx_one launches it; compiled out of the fixed-QAM ones)
     constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV, true>();
     const TxRxCommon& c = a.r.c;
@@ -20,40 +20,32 @@ static hipError_t rx_sweep_launch(const RxSweepArgs& a, int* grid, hipStream_t s
     rx_carve<R, LOGN, EQ, FB, MV, true>(lds, c.words_per_sym, rx_tts<R, LOGN, FB>(c.scm), 0, a.n_snr);
     if (lds.bytes + rx_static_lds<R, FB>() > kLdsPerCu) {
         // (a layout that does not fit: the generic kernel, which is the last resort)
-        if constexpr (FB > 0) return rx_sweep_launch<R, LOGN, -1, 0>(a, grid, s);
+        if constexpr (FB > 0) return rx_sweep_launch<R, LOGN, -1, 0>(a, s);
         else return kLdsOverflow;
     }
     // Every workgroup builds a table per point and ends with an atomic pair per point: two rounds of
     // the resident workgroups (as the profile's launcher)
-    return rx_go<BLK, Geo<LOGN, BLK>::SPB>(k_rx_sweep<R, LOGN, EQ, FB, MV>, lds.bytes, 2, c.n_sym, a, grid, s);
+    return rx_go<BLK, Geo<LOGN, BLK>::SPB>(k_rx_sweep<R, LOGN, EQ, FB, MV>, lds.bytes, 2, c.n_sym, a, s);
 }
 
 template <typename R, int LOGN>
-static hipError_t rx_sweep_one(const RxSweepArgs& a, int* grid, hipStream_t s) {
+static hipError_t rx_sweep_one(const RxSweepArgs& a, hipStream_t s) {
     if constexpr (ref_fb<R, LOGN>() > 1) {
         if (bench_fixed_shape<ref_fb<R, LOGN>()>(a.r.c))
             return with_eq(a.r.c.eq, [&](auto eq) {
-                return rx_sweep_launch<R, LOGN, decltype(eq)::value, ref_fb<R, LOGN>()>(a, grid, s);
+                return rx_sweep_launch<R, LOGN, decltype(eq)::value, ref_fb<R, LOGN>()>(a, s);
             });
     }
-    return rx_sweep_launch<R, LOGN, -1, 0>(a, grid, s);
+    return rx_sweep_launch<R, LOGN, -1, 0>(a, s);
 }
 
 template <typename R>
-hipError_t launch_rx_sweep(int logn, const RxSweepArgs& a, int* grid, hipStream_t s) {
+hipError_t launch_rx_sweep(int logn, const RxSweepArgs& a, hipStream_t s) {
     if (a.n_snr < 1 || a.n_snr > OFDM_MAX_SWEEP_POINTS || a.r.wide != nullptr) return hipErrorInvalidValue;
-#define OFDM_RX_SWEEP_CASE(L) \
-    case L:                   \
-        return rx_sweep_one<R, L>(a, grid, s);
-    switch (logn) {
-        OFDM_LOGN_CASES(OFDM_RX_SWEEP_CASE)
-        default:
-            return kOutOfRange;
-    }
-#undef OFDM_RX_SWEEP_CASE
+    return with_logn(logn, [&](auto l) { return rx_sweep_one<R, decltype(l)::value>(a, s); });
 }
 
 #define OFDM_INSTANTIATE_RX_SWEEP(R) \
-    template hipError_t launch_rx_sweep<R>(int, const RxSweepArgs&, int*, hipStream_t);
+    template hipError_t launch_rx_sweep<R>(int, const RxSweepArgs&, hipStream_t);
 
 }  // namespace ofdm

@@ -33,15 +33,8 @@ static hipError_t tx_clip_launch(const TxArgs& a0, const TxClipTail& k0, double 
         if (!(a2_h0 > 0.0)) return hipErrorInvalidValue;
         k.a2 = a2_h0;
     }
-    auto fn = k_tx<R, LOGN, FB, LT, false, false, false, true, TxClipTail>;
-    hipError_t e = set_smem(fn, sm);
-    if (e != hipSuccess) return e;
-    const int resident = resident_blocks(fn, BLK, sm);
-    if (a.chunk > 1) a.chunk = tx_chunk(a.c.n_sym, a.chunk, Geo<LOGN, BLK>::SPB, resident);
-    const int64_t groups = (a.c.n_sym + a.chunk - 1) / a.chunk;
-    *grid = clamp_grid((groups + Geo<LOGN, BLK>::SPB - 1) / Geo<LOGN, BLK>::SPB);
-    hipLaunchKernelGGL(fn, dim3(*grid), dim3(BLK), sm, s, a, k);
-    return hipGetLastError();
+    return tx_go<BLK, Geo<LOGN, BLK>::SPB>(k_tx<R, LOGN, FB, LT, false, false, false, true, TxClipTail>, sm, a, grid, s,
+                                           k);
 }
 
 // Routing, the one definition: the throughput forms take the two complex128 N = 1024 64-QAM bench shapes
@@ -78,15 +71,7 @@ hipError_t launch_tx_clip(int logn, const TxArgs& a, double a2, double a2_h0, un
     TxClipTail k{};
     k.a2 = a2;
     k.counters = counters;
-#define OFDM_TXCLIP_CASE(L) \
-    case L:                 \
-        return tx_clip_one<R, L>(a, k, a2_h0, grid, s);
-    switch (logn) {
-        OFDM_LOGN_CASES(OFDM_TXCLIP_CASE)
-        default:
-            return kOutOfRange;
-    }
-#undef OFDM_TXCLIP_CASE
+    return with_logn(logn, [&](auto l) { return tx_clip_one<R, decltype(l)::value>(a, k, a2_h0, grid, s); });
 }
 
 #define OFDM_INSTANTIATE_TXCLIP(R) \

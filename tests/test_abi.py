@@ -94,17 +94,22 @@ def test_product_library_has_no_ablation_switches():
 
 def test_ab_only_variant_reports_kernels_it_lacks():
     """OFDM_AB_ONLY experiment builds (tools/ab.sh variants) instantiate N = 1024..4096 only.  Every
-    log2 N dispatch switch falls through to kOutOfRange, which such a build defines as kNotInBuild,
-    and the ABI turns that into OFDM_E_INVALID "kernel not in this build" (ValueError in Python)
-    instead of a HIP "invalid argument"; a product build keeps hipErrorInvalidValue there (N is
-    checked at plan creation, so it is never reached).  Checked on the sources, with the
-    preprocessor branches evaluated both ways."""
+    launcher's log2 N dispatch is with_logn (ofdm_kernels_inst.hpp), the only switch on logn in csrc/,
+    which falls through to kOutOfRange; such a build defines that as kNotInBuild, and the ABI's checked()
+    turns it into OFDM_E_INVALID "kernel not in this build" (ValueError in Python) instead of a HIP
+    "invalid argument"; a product build keeps hipErrorInvalidValue there (N is checked at plan creation,
+    so it is never reached).  The launchers' verdicts (kNotInBuild, kLdsOverflow, kNoFusedForm) are values
+    no HIP call can return.  Checked on the sources, with the preprocessor branches evaluated both ways."""
     csrc = os.path.join(ROOT, "ofdm-based-systems_amd", "csrc")
-    inst = open(os.path.join(csrc, "ofdm_kernels_inst.hpp")).read()
-    launch = open(os.path.join(csrc, "ofdm_launch.hpp")).read()
-    abi = open(os.path.join(csrc, "ofdm_abi.hip")).read()
-    switches = re.findall(r"switch \(logn\) \{.*?default:\s*return (\w+);", inst, flags=re.S)
-    assert len(switches) == 3 and set(switches) == {"kOutOfRange"}, switches
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))
+               if f.endswith((".hpp", ".hip", ".h"))}
+    inst, launch, abi = (sources[f] for f in ("ofdm_kernels_inst.hpp", "ofdm_launch.hpp", "ofdm_abi.hip"))
+    switches = {f: re.findall(r"switch \(logn\)", text) for f, text in sources.items()}
+    assert {f: len(s) for f, s in switches.items() if s} == {"ofdm_kernels_inst.hpp": 1}, switches
+    with_logn = inst[inst.index("static hipError_t with_logn(int logn, F f)"):]
+    with_logn = with_logn[:with_logn.index("\n}\n")]
+    assert re.findall(r"switch \(logn\) \{.*?default:\s*return (\w+);", with_logn, flags=re.S) == ["kOutOfRange"]
+    assert "OFDM_LOGN_CASES(" in with_logn
 
     def branch(text, name, ab_only):
         m = re.search(r"#ifdef OFDM_AB_ONLY\n(.*?)#else\n(.*?)#endif", text[text.index(name) - 200:], flags=re.S)
@@ -114,6 +119,32 @@ def test_ab_only_variant_reports_kernels_it_lacks():
     assert "kOutOfRange = hipErrorInvalidValue" in branch(inst, "constexpr hipError_t kOutOfRange", False)
     assert "kAbOnly = true" in branch(launch, "constexpr bool kAbOnly", True)
     assert "kAbOnly = false" in branch(launch, "constexpr bool kAbOnly", False)
-    hipchk = abi[abi.index("#define HIPCHK"):abi.index("} while (0)", abi.index("#define HIPCHK"))]
-    assert "kAbOnly && _e == kNotInBuild" in hipchk and "OFDM_E_INVALID" in hipchk
-    assert "kernel not in this build" in hipchk
+
+    # the translation sits in checked(), guarded by kAbOnly, and nowhere else (HIPCHK serves HIP calls)
+    checked = abi[abi.index("int checked(const char* who, ofdm_plan_t p, hipError_t e) {"):]
+    checked = checked[:checked.index("\n}\n")]
+    m = re.search(r"if \(kAbOnly && e == kNotInBuild\)\s*return fail\(OFDM_E_INVALID,(.*?)\);", checked, flags=re.S)
+    assert m and "kernel not in this build" in m.group(1), checked
+    abi_code = re.sub(r"//[^\n]*", "", abi)
+    assert abi_code.count("kernel not in this build") == 1
+    for name in ("kNotInBuild", "kLdsOverflow", "kNoFusedForm"):
+        assert abi_code.count(name) == 1 and name in re.sub(r"//[^\n]*", "", checked), name
+
+    # the three verdicts: pairwise distinct, inside hipError_t's range, and no enumerator of it
+    values = {name: int(v) for name, v in
+              re.findall(r"constexpr hipError_t (k\w+) = static_cast<hipError_t>\((\d+)\);", launch)}
+    assert set(values) == {"kNotInBuild", "kLdsOverflow", "kNoFusedForm"}, values
+    assert len(set(values.values())) == 3
+    header = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include", "hip", "hip_runtime_api.h")
+    if os.path.exists(header):
+        enum = open(header).read()
+        enum = re.search(r"typedef enum\s+(?:\w+\s+)?hipError_t\s*\{(.*?)\}\s*hipError_t;", enum, flags=re.S).group(1)
+        taken = {int(v) for v in re.findall(r"^\s*hip(?:Success|Error\w+)\s*=\s*(\d+)\s*,", enum, flags=re.M)}
+        assert {0, 1, 701, 801} <= taken and len(taken) > 50, sorted(taken)
+    else:
+        taken = {0, 1, 701, 801}  # hipSuccess, InvalidValue, LaunchOutOfResources, NotSupported
+    # (an enum without a fixed type holds every value of the smallest bit-field that holds its
+    # enumerators: the largest is below 2048)
+    assert max(taken) < 2048
+    for name, v in values.items():
+        assert v not in taken and 0 < v < 2048, (name, v)

@@ -7,6 +7,12 @@ every kernel, from `llvm-readelf --notes` on the library's gfx950 code objects.
 
 Kernels of PARENT.so are compared by name; kernels only in THIS.so are listed with their figures.
 Needs no GPU.  Exit status 1 if a kernel of the parent build differs or is missing.
+
+    tools/kernel_meta_diff.py --text PARENT.so THIS.so
+
+compares the kernels' machine code as well (`llvm-objdump -d`, per kernel name, so the order of
+instantiation inside a translation unit may move) and counts them per kernel family: the audit of a
+change that must not touch device code.
 """
 import argparse
 import os
@@ -37,6 +43,11 @@ def code_objects(path, arch="gfx950"):
         pos = data.find(MAGIC, pos + 1)
 
 
+def short(demangled):
+    """A kernel's name without return type, namespaces in front and parameter list."""
+    return re.sub(r"^(void )?((\(anonymous namespace\)|ofdm)::)*|\(.*\)$", "", demangled)
+
+
 def kernels(path):
     """{demangled kernel name: (the four FIELDS)} of a library."""
     out = {}
@@ -54,11 +65,46 @@ def kernels(path):
     names = list(out)
     dem = subprocess.run(["c++filt"], input="\n".join(names), check=True,
                          capture_output=True, text=True).stdout.split("\n")
-    return {re.sub(r"^void ofdm::|\(.*\)$", "", d): out[n] for n, d in zip(names, dem)}
+    return {short(d): out[n] for n, d in zip(names, dem)}
+
+
+def texts(path):
+    """{demangled kernel name: its disassembly, encodings included, addresses dropped} of a library."""
+    out = {}
+    for co in code_objects(path):
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(co)
+            f.flush()
+            dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", f.name], check=True,
+                                 capture_output=True, text=True).stdout
+        for part in re.split(r"\n(?=[0-9a-f]{8,} <)", dis):
+            head = re.match(r"[0-9a-f]+ <(\S+)>:\n", part)
+            if head:
+                out[head.group(1)] = re.sub(r"// [0-9A-F]+:", "//", part[head.end():])
+    names = list(out)
+    dem = subprocess.run(["c++filt"], input="\n".join(names), check=True,
+                         capture_output=True, text=True).stdout.split("\n")
+    return {short(d): out[n] for n, d in zip(names, dem)}
+
+
+def text_audit(parent, this, names):
+    """Per-family counts and the kernels (`names`: those with metadata) whose machine code differs."""
+    old, new = texts(parent), texts(this)
+    fam = {}
+    for k in names:
+        fam[k.split("<")[0]] = fam.get(k.split("<")[0], 0) + 1
+    diff = [k for k in names if k not in old or old[k] != new.get(k)]
+    print(f"# machine code (llvm-objdump -d, per kernel name) of the parent's {len(names)} kernels, per family:\n# "
+          + ", ".join(f"{f} {n}" for f, n in sorted(fam.items(), key=lambda x: -x[1])))
+    print(f"# with different machine code in this build: {len(diff)}")
+    for k in diff:
+        print("# DIFFERENT TEXT:", k)
+    return diff
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--text", action="store_true", help="compare the kernels' disassembly too")
     ap.add_argument("parent")
     ap.add_argument("this")
     a = ap.parse_args()
@@ -78,7 +124,11 @@ def main():
     print("# new kernels: name  " + "  ".join(FIELDS))
     for k in sorted(set(new) - set(old)):
         print(k, *new[k])
-    return 1 if diff_f or diff_o else 0
+    diff_t = text_audit(a.parent, a.this, sorted(old)) if a.text else []
+    word = lambda n: str(n) if n else "none"
+    print(f"# {word(len(set(diff_f + diff_o + diff_t)))} different, {word(len(set(new) - set(old)))} new, "
+          f"{word(len(set(old) - set(new)))} missing")
+    return 1 if diff_f or diff_o or diff_t else 0
 
 
 if __name__ == "__main__":
