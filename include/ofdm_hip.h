@@ -284,6 +284,37 @@ int ofdm_rx_profile(ofdm_plan_t plan, void* stream, const void* y, const double*
                     int64_t* profile);
 
 /*
+ * ofdm_rx with a per-frame error record of the run (an entry point added to ABI 6: nothing of the
+ * version's existing interface changes, so the number stands): when the errors fall, where
+ * ofdm_rx_profile says where.  From it come the frame (packet) error rate, a standard error on the BER
+ * that holds when bit errors are not independent, and the distribution of errors per frame.
+ *
+ * A frame is F = frame_len >= 1 consecutive GLOBAL OFDM symbols: symbol s belongs to frame
+ * f = floor(s / F), whatever the call's sym0.
+ * frames: device uint64[n_frames][2], accumulated and never zeroed by the library.  For every symbol s
+ * of the call,
+ *   frames[f][0] += the bit errors of symbol s: exactly that symbol's share of counters[0], under the
+ *                   same n_valid_bits and adaptive partial-byte masking
+ *   frames[f][1] += its share of counters[1].
+ * So the sum over f of frames[f][j] over a call equals that call's increment of counters[j], exactly;
+ * and, the additions being integer, the record does not depend on the grid, the batching, the split of
+ * a run over calls or ranks, or whether a frame straddles any of those.
+ * OFDM_E_INVALID, before any launch: what ofdm_rx refuses; frames == NULL; frame_len < 1; n_frames < 1;
+ *   floor((sym0 + n_sym - 1) / frame_len) >= n_frames (the record is too short for the call's last
+ *   symbol); n_sym above 2^31 (one call).  n_sym = 0: an empty call.
+ * Kernels (k_rx_frames): the complex128 bench shapes (cyclic-prefix OFDM; 64-QAM at N = 1024, adaptive
+ * square-QAM loading at N = 2048, 256-QAM at N = 4096) with throughput streams (bits == NULL,
+ * nr == NULL) and no z_out run their throughput receiver's form, in ofdm_rx's own workgroup shape;
+ * every other call the generic kernel's.  Everything else -- arguments, counters, z_out / z_keep -- is
+ * ofdm_rx's.
+ */
+int ofdm_rx_frames(ofdm_plan_t plan, void* stream, const void* y, const double* nr, const double* ni,
+                   uint64_t seed, const ofdm_stats* stats, int64_t total_samples, double snr_db,
+                   int32_t noise_on, const uint8_t* bits, int64_t sym0, int64_t n_sym,
+                   int64_t n_valid_bits, uint64_t* counters, void* z_out, int64_t z_keep,
+                   int64_t frame_len, int64_t n_frames, uint64_t* frames);
+
+/*
  * The one-pass SNR sweep receiver (an entry point added to ABI 6: nothing of the version's existing
  * interface changes, so the number stands): ofdm_rx of the same channel samples at n_snr SNR points in
  * one launch.  The transmitted stream, the tx bits and the noise words of throughput mode depend on

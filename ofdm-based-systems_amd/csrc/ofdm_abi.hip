@@ -894,11 +894,37 @@ static int rx_args(const char* who, ofdm_plan_t p, const void* y, const double* 
     return OFDM_OK;
 }
 
-// ofdm_rx and ofdm_rx_profile (who; profile: the record, or null for ofdm_rx)
+// ofdm_rx_frames' record (ofdm_hip.h)
+struct RxFrames {
+    int64_t frame_len, n_frames;
+    uint64_t* frames;
+};
+// The frame record's own refusals, made before the plan is looked at (a negative sym0 or n_sym is left
+// to rx_args)
+static int frames_ok(const char* who, const RxFrames& fr, int64_t sym0, int64_t n_sym) {
+    const auto no = [&](const std::string& why) { return fail(OFDM_E_INVALID, std::string(who) + ": " + why); };
+    if (!fr.frames) return no("needs a frame record");
+    if (fr.frame_len < 1) return no("frame_len " + std::to_string(fr.frame_len) + " is not a positive symbol count");
+    if (fr.n_frames < 1) return no("n_frames " + std::to_string(fr.n_frames) + " is not a positive frame count");
+    if (n_sym > (int64_t)1 << 31) return no("a call takes at most 2^31 symbols, got " + std::to_string(n_sym));
+    if (sym0 >= 0 && n_sym > 0) {
+        // the last symbol sym0 + n_sym - 1 and its frame in unsigned arithmetic: sym0 < 2^63 and
+        // n_sym <= 2^31 here, so neither the sum nor floor(sym0 / F) + the carry of the remainder wraps
+        const uint64_t F = (uint64_t)fr.frame_len;
+        const uint64_t last = (uint64_t)sym0 + (uint64_t)(n_sym - 1);
+        const uint64_t frame = (uint64_t)sym0 / F + ((uint64_t)sym0 % F + (uint64_t)(n_sym - 1)) / F;
+        if (frame >= (uint64_t)fr.n_frames)
+            return no("the call's last symbol " + std::to_string(last) + " lies in frame " + std::to_string(frame) +
+                      ", beyond the record's " + std::to_string(fr.n_frames) + " frames");
+    }
+    return (int)OFDM_OK;
+}
+// ofdm_rx, ofdm_rx_profile and ofdm_rx_frames (who; profile: the record, or null; fr: the frame record, or
+// null -- without either, ofdm_rx, whose checks, arguments and launch are then what they were)
 static int rx_call(const char* who, ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni,
                    uint64_t seed, const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on,
                    const uint8_t* bits, int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters,
-                   void* z_out, int64_t z_keep, int64_t* profile) {
+                   void* z_out, int64_t z_keep, int64_t* profile, const RxFrames* fr = nullptr) {
     RxArgs a{};
     bool run;
     const int rc = rx_args(who, p, y, nr, ni, seed, stats, total_samples, noise_on, bits, sym0, n_sym, n_valid_bits,
@@ -910,6 +936,18 @@ static int rx_call(const char* who, ofdm_plan_t p, void* stream, const void* y, 
     a.flags = OFDM_ENV_FLAGS("OFDM_ABLATE_RX");
     a.wide = p->wide_plan ? (const WideAxis*)p->wide.p : nullptr;  // an order above 256: the wide slicer
     a.profile = profile;
+    if (fr) {
+        // the 64-bit part of the frame index, done here once (RxFramesTail)
+        RxFramesTail ft{};
+        ft.frames = (unsigned long long*)fr->frames;
+        ft.base = sym0 / fr->frame_len;
+        ft.n_frames = fr->n_frames;
+        ft.first = (uint32_t)std::min<int64_t>(fr->frame_len - sym0 % fr->frame_len, (int64_t)1 << 31);
+        ft.flen = (uint32_t)std::min<int64_t>(fr->frame_len, 0xFFFFFFFFll);
+        return checked(who, p, with_prec(p, [&](auto r) {
+            return launch_rx_frames<decltype(r)>(p->logn, a, ft, (hipStream_t)stream);
+        }));
+    }
     return checked(who, p, with_prec(p, [&](auto r) {
         using R = decltype(r);
         return profile ? launch_rx_prof<R>(p->logn, a, (hipStream_t)stream) : launch_rx<R>(p->logn, a, (hipStream_t)stream);
@@ -931,6 +969,16 @@ int ofdm_rx_profile(ofdm_plan_t p, void* stream, const void* y, const double* nr
     if (!profile) return fail(OFDM_E_INVALID, "ofdm_rx_profile needs a profile record");
     return rx_call("ofdm_rx_profile", p, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0,
                    n_sym, n_valid_bits, counters, z_out, z_keep, profile);
+}
+
+int ofdm_rx_frames(ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni, uint64_t seed,
+                   const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on,
+                   const uint8_t* bits, int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters,
+                   void* z_out, int64_t z_keep, int64_t frame_len, int64_t n_frames, uint64_t* frames) {
+    const RxFrames fr{frame_len, n_frames, frames};
+    if (const int rc = frames_ok("ofdm_rx_frames", fr, sym0, n_sym)) return rc;
+    return rx_call("ofdm_rx_frames", p, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0,
+                   n_sym, n_valid_bits, counters, z_out, z_keep, nullptr, &fr);
 }
 
 int ofdm_rx_sweep(ofdm_plan_t p, void* stream, const void* y, uint64_t seed, const ofdm_stats* stats,

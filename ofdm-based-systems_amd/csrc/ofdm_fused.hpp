@@ -1446,7 +1446,7 @@ __device__ __forceinline__ void prof_power(cpx<R> z, cpx<R> c, unsigned long lon
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
 __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB, LOGN, EQ, MV>())) void k_rx(
     RxArgs a) {
-    constexpr bool PROF = false, SWEEP = false;
+    constexpr bool PROF = false, SWEEP = false, FRAMES = false;
 #include "ofdm_rx_body.hpp"
 }
 
@@ -1456,8 +1456,25 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB,
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
 __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<R, FB, LOGN, EQ, MV, true>())) void k_rx_prof(
     RxArgs a) {
-    constexpr bool PROF = true, SWEEP = false;
+    constexpr bool PROF = true, SWEEP = false, FRAMES = false;
 #include "ofdm_rx_body.hpp"
+}
+
+// The receiver that also accumulates the per-frame error record (ofdm_rx_frames, ofdm_hip.h: the
+// definition): k_rx with FRAMES compiled in -- where a symbol's bit and symbol errors are final they are
+// summed over the symbol's lanes inside the wave and added to the symbol's frame, at most two 64-bit
+// integer atomics per symbol and wave, none for a symbol without errors.  No LDS and no barrier beyond
+// k_rx's, so k_rx's own workgroup shapes and waves per SIMD.  The frame arguments are a second kernel
+// parameter (RxFramesTail) that only this kernel has: RxArgs and every other receiver stay what they
+// were.  Instantiated for the generic kernel (and its WIDE form) and for the complex128 cyclic-prefix
+// OFDM throughput receivers of the bench shapes (ofdm_frames_inst.hpp).
+template <typename R, int LOGN, int EQ, int FB, bool MV, bool WIDE = false>
+__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB, LOGN, EQ, MV>())) void k_rx_frames(
+    RxArgs a, RxFramesTail ft) {
+    constexpr bool PROF = false, SWEEP = false, FRAMES = true, REF = false;
+#define OFDM_RX_BODY_FRAMES
+#include "ofdm_rx_body.hpp"
+#undef OFDM_RX_BODY_FRAMES
 }
 
 // The one-pass SNR sweep receiver (ofdm_rx_sweep): every symbol is received once per SNR point of the
@@ -1471,7 +1488,7 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<
 template <typename R, int LOGN, int EQ, int FB, bool MV>
 __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<R, FB, LOGN, EQ, MV, true>())) void k_rx_sweep(
     RxSweepArgs sa) {
-    constexpr bool PROF = false, SWEEP = true, REF = false, WIDE = false;
+    constexpr bool PROF = false, SWEEP = true, FRAMES = false, REF = false, WIDE = false;
     const RxArgs& a = sa.r;  // (a copy of its own that took each point's snr_lin in turn left the argument registers for memory)
 #define OFDM_RX_BODY_SWEEP
 #include "ofdm_rx_body.hpp"

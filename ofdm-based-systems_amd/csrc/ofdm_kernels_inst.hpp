@@ -318,14 +318,15 @@ hipError_t launch_tx(int logn, const TxArgs& a, int* grid, hipStream_t s) {
 // launcher has sized the layout: `sm` bytes of dynamic LDS opted in, a grid of ceil(n_sym / SPB)
 // workgroups capped at `rounds` rounds of the workgroups resident at once, each then looping over its
 // share of the symbols (rounds = 0, or a runtime that cannot say: uncapped up to kMaxGrid), and the launch.
-template <int BLK, int SPB, typename K, typename A>
-static hipError_t rx_go(K fn, size_t sm, int rounds, int64_t n_sym, const A& a, hipStream_t s) {
+// (tail: the kernel arguments behind `a`, as tx_go's -- k_rx_frames' RxFramesTail)
+template <int BLK, int SPB, typename K, typename A, typename... T>
+static hipError_t rx_go(K fn, size_t sm, int rounds, int64_t n_sym, const A& a, hipStream_t s, const T&... tail) {
     const hipError_t e = set_smem(fn, sm);
     if (e != hipSuccess) return e;
     int64_t want = (n_sym + SPB - 1) / SPB;
     const int res = rounds > 0 ? resident_blocks(fn, BLK, sm) : 0;
     if (res > 0) want = std::min<int64_t>(want, (int64_t)rounds * res);
-    hipLaunchKernelGGL(fn, dim3(clamp_grid(want)), dim3(BLK), sm, s, a);
+    hipLaunchKernelGGL(fn, dim3(clamp_grid(want)), dim3(BLK), sm, s, a, tail...);
     return hipGetLastError();
 }
 

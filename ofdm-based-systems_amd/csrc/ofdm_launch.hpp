@@ -199,6 +199,21 @@ struct RxArgs {
     int64_t* profile;
 };
 
+// ofdm_rx_frames: the frame record's arguments, a second kernel parameter behind RxArgs (k_rx_frames
+// only; every other receiver takes its arguments alone, as before).  The host does the 64-bit part of
+// the frame index: global symbol sym0 + sl (sl: the call-relative index, < 2^31) lies in frame
+//   base                              for sl < first,
+//   base + 1 + (sl - first) / flen    otherwise (a 32-bit division),
+// base = floor(sym0 / F), first = min(F - sym0 mod F, 2^31): the call's symbols before its first frame
+// boundary, flen = min(F, 2^32 - 1) (an F beyond the call's reach has no second boundary in it).
+struct RxFramesTail {
+    unsigned long long* frames;  // device uint64[n_frames][2] (bit errors, symbol errors), accumulated
+    int64_t base;
+    int64_t n_frames;
+    uint32_t first;
+    uint32_t flen;
+};
+
 // ofdm_rx_sweep: the receiver's arguments (counters: device uint64[n_snr][2]; snr_lin, noise_on,
 // nr / ni, z_out, wide and profile of `r` unused: noise is always on) and the points' 10^(snr_db/10)
 struct RxSweepArgs {
@@ -284,6 +299,10 @@ hipError_t launch_rx(int logn, const RxArgs& a, hipStream_t s);
 // the receiver with the per-subcarrier profile (a.profile set; ofdm_prof_inst.hpp)
 template <typename R>
 hipError_t launch_rx_prof(int logn, const RxArgs& a, hipStream_t s);
+
+// the receiver with the per-frame error record (ofdm_frames_inst.hpp)
+template <typename R>
+hipError_t launch_rx_frames(int logn, const RxArgs& a, const RxFramesTail& f, hipStream_t s);
 
 // the one-pass SNR sweep receiver (ofdm_sweep_inst.hpp)
 template <typename R>

@@ -1,7 +1,9 @@
 // ofdm_rx_body.hpp -- the body of the fused receivers k_rx and k_rx_prof (ofdm_fused.hpp), included
 // into each kernel after its `constexpr bool PROF` (no include guard: included once per kernel).
 // In scope: the kernel's template parameters R, LOGN, EQ, FB, MV, REF, WIDE, its argument `RxArgs a`,
-// PROF and SWEEP.
+// PROF, SWEEP and FRAMES.
+// FRAMES (k_rx_frames only, which defines OFDM_RX_BODY_FRAMES around its include and has its second
+// argument `RxFramesTail ft` in scope): each symbol's counts are also added to its frame's pair.
 // SWEEP (k_rx_sweep only, which defines OFDM_RX_BODY_SWEEP around its include and has its argument
 // `RxSweepArgs sa` in scope, `a` being sa.r): every symbol is received once per SNR
 // point, the point loop opened and closed under that macro so that the other kernels' text has no loop.
@@ -10,6 +12,13 @@
                   "the profile: the generic kernel, or a complex128 cyclic-prefix OFDM QAM throughput receiver");
     static_assert(!SWEEP || (!REF && !WIDE && !PROF && (FB == 0 || (sizeof(R) == 8 && FB > 1 && !(FB & 1) && !MV))),
                   "the sweep: the generic kernel, or a complex128 cyclic-prefix OFDM fixed-QAM throughput receiver");
+#ifdef OFDM_RX_BODY_FRAMES
+    static_assert(FRAMES && !REF && !PROF && !SWEEP &&
+                      (FB == 0 || (sizeof(R) == 8 && (FB == 1 || !(FB & 1)) && (FB == 1 || !MV))),
+                  "the frame record: the generic kernel, or a complex128 cyclic-prefix OFDM QAM throughput receiver");
+#else
+    static_assert(!FRAMES, "k_rx_frames defines OFDM_RX_BODY_FRAMES around its include");
+#endif
 #ifdef OFDM_RX_BODY_SWEEP
 #define OFDM_RX_SNR_LIN snr_lin_pt  // the SNR of the point being received
 #else
@@ -617,6 +626,36 @@
             }
             be += bes;
             se += ses;
+#ifdef OFDM_RX_BODY_FRAMES
+            // FRAMES: this symbol's counts into its frame.  A lane's share is <= 192 bit and 16 symbol
+            // errors and a wave's <= 12288 and 1024, so both fit one word through the sum over the
+            // symbol's lanes of this wave (segments of TPS lanes where several symbols share a wave, every
+            // lane of a segment active with it; a symbol of 2 / 4 waves adds once per wave).  The first
+            // lane of the segment adds the non-zero fields; the frame index: RxFramesTail.
+            // (butterflies inside 32 lanes through ds_swizzle's bit mode, xor mask 1 << j, which needs no
+            // lane-address register; the two halves of a whole wave through two v_readlane)
+            {
+                constexpr int SEG = TPS < 64 ? TPS : 64, SEG32 = SEG < 32 ? SEG : 32;
+                constexpr int LOGS = SEG32 == 32 ? 5 : SEG32 == 16 ? 4 : SEG32 == 8 ? 3 : SEG32 == 4 ? 2 : SEG32 == 2 ? 1 : 0;
+                uint32_t v = bes + (ses << 16);
+                static_for<0, LOGS>([&](auto J) {
+                    constexpr int pattern = ((1 << J) << 10) | 0x1F;  // and 0x1F, or 0, xor 1 << J
+                    v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, pattern);
+                });
+                if constexpr (SEG == 64)
+                    v = (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 32);
+                if ((threadIdx.x & (SEG - 1)) == 0 && v) {
+                    const uint32_t rel = (uint32_t)sl;
+                    const int64_t f = ft.base + (rel < ft.first ? 0 : 1 + (int64_t)((rel - ft.first) / ft.flen));
+                    // a memory-safety guard only, never taken: the ABI (frames_ok, the one check of the frame
+                    // arguments) refuses a record too short for the call's last symbol before any launch
+                    if (f < ft.n_frames) {
+                        if (v & 0xFFFFu) atomicAdd(ft.frames + 2 * f, (unsigned long long)(v & 0xFFFFu));
+                        if (v >> 16) atomicAdd(ft.frames + 2 * f + 1, (unsigned long long)(v >> 16));
+                    }
+                }
+            }
+#endif
         }
 #ifdef OFDM_RX_BODY_SWEEP
         // this symbol's counts at this point (a lane's: <= 128 bit and 16 symbol errors, so both fit one

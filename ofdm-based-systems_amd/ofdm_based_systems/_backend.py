@@ -46,6 +46,9 @@ FX_HI, FX_LO = 2.0 ** -8, 2.0 ** -40
 # ofdm_rx_profile's record: int64[PROFILE_ROWS][N] -- bit errors, symbol errors, the two limbs of
 # the error-vector power (the power_fx format), clipped samples
 PROFILE_ROWS = 5
+# frames one run's per-frame record holds at most (LinkEngine.run(frame_symbols=...)): 2^24 frames of
+# two int64, 256 MiB
+MAX_FRAMES = 1 << 24
 EQ_NONE, EQ_ZF, EQ_MMSE = 0, 1, 2
 PREFIX_CYCLIC, PREFIX_ZERO = 0, 1
 MOD_OFDM, MOD_SC = 0, 1
@@ -120,6 +123,9 @@ SIGNATURES = {
                                _I64, _VP, _VP, _I64]),
     "ofdm_rx_profile": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _I64, _F64, _I32, _VP, _I64, _I64,
                                        _I64, _VP, _VP, _I64, _VP]),
+    # (ofdm_rx's arguments, frame_len, n_frames, frames; ofdm_rx_frames joined ABI 6 as an added entry point)
+    "ofdm_rx_frames": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _I64, _F64, _I32, _VP, _I64, _I64,
+                                      _I64, _VP, _VP, _I64, _I64, _I64, _VP]),
     # (snr_db: a host array of doubles, copied at the call)
     "ofdm_rx_sweep": (ctypes.c_int, [_VP, _VP, _VP, _U64, _VP, _I64, _c_f64p, _I32, _I64, _I64, _I64, _VP]),
     # (plan, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits, counters)

@@ -78,6 +78,9 @@ class SimulationSettings(BaseSettings):
     batch_symbols: Optional[int] = Field(None, description="OFDM symbols per device batch")
     clip_db: Optional[float] = Field(None, description="soft-limit the transmitted samples' envelope at this level "
                                      "in dB above the nominal mean sample power (None: a linear transmitter)")
+    frame_symbols: Optional[int] = Field(None, ge=1, description="OFDM symbols per frame: also report the frame "
+                                         "error rate, the BER's standard error and the bit errors per frame "
+                                         "(None: no frame record)")
 
     def __str__(self) -> str:
         lines = [

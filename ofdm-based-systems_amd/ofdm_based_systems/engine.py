@@ -99,6 +99,69 @@ class SubcarrierProfile:
 
 
 @dataclass
+class FrameStats:
+    """Per-frame error counts of a whole run (``ofdm_rx_frames``, include/ofdm_hip.h): a frame is
+    ``frame_symbols`` consecutive global OFDM symbols, frame f holding symbols [f F, (f + 1) F).
+    Accumulated on the device in integers: identical for any batching and rank count.  The arrays
+    cover every frame the run touches; the derived quantities the ``n_full`` full frames only -- a
+    trailing partial frame stays in the arrays and out of the rates."""
+    frame_symbols: int          # F
+    n_symbols: int              # OFDM symbols of the run
+    bits_per_symbol: int        # bits one OFDM symbol carries
+    bit_errors: np.ndarray      # int64 [ceil(n_symbols / F)]; sums to LinkStats.bit_errors
+    symbol_errors: np.ndarray   # int64 [ceil(n_symbols / F)]; sums to LinkStats.symbol_errors
+    # bits of the run that were compared (LinkEngine.valid_bits, or the caller's n_valid_bits); None:
+    # all of them
+    n_valid_bits: Optional[int] = None
+
+    @property
+    def n_full(self) -> int:
+        """Full frames of the run: n_symbols // F."""
+        return self.n_symbols // self.frame_symbols
+
+    @property
+    def frame_errors(self) -> int:
+        """Full frames with at least one bit error."""
+        return int(np.count_nonzero(self.bit_errors[:self.n_full] > 0))
+
+    @property
+    def fer(self) -> Optional[float]:
+        """Frame error rate over the full frames; None without one."""
+        return self.frame_errors / self.n_full if self.n_full else None
+
+    def errors_per_frame_hist(self) -> np.ndarray:
+        """hist[e] = full frames with exactly e bit errors (``np.bincount``)."""
+        return np.bincount(self.bit_errors[:self.n_full])
+
+    @property
+    def ber_stderr(self) -> Optional[float]:
+        """Standard error of the run's BER from the spread of the error count across the n full
+        frames, sqrt(sum (e_f - mean)^2 / (n (n - 1))) / (F bits per symbol): valid when bit errors
+        cluster inside a frame.  None with fewer than two full frames, or when ``n_valid_bits`` leaves
+        a bit of the run uncompared (the frames then do not compare the same number of bits)."""
+        n = self.n_full
+        if n < 2 or self.frame_symbols * self.bits_per_symbol == 0:
+            return None
+        if self.n_valid_bits is not None and self.n_valid_bits < self.n_symbols * self.bits_per_symbol:
+            return None
+        e = self.bit_errors[:n].astype(np.float64)
+        var = float(np.sum((e - e.mean()) ** 2)) / (n * (n - 1))
+        return math.sqrt(var) / (self.frame_symbols * self.bits_per_symbol)
+
+
+def frame_count(n_sym: int, frame_symbols) -> int:
+    """Frames a run of n_sym OFDM symbols touches, ceil(n_sym / F) (at least one record row); ValueError
+    for an F below 1 or a record above B.MAX_FRAMES frames."""
+    if isinstance(frame_symbols, bool) or int(frame_symbols) != frame_symbols or int(frame_symbols) < 1:
+        raise ValueError(f"frame_symbols = {frame_symbols!r} is not a positive number of OFDM symbols")
+    n = max(1, -(-int(n_sym) // int(frame_symbols)))
+    if n > B.MAX_FRAMES:
+        raise ValueError(f"frame_symbols = {frame_symbols} gives {n} frames over {n_sym} OFDM symbols, above the "
+                         f"cap of {B.MAX_FRAMES} (2^24 frames, a 256 MiB record); use longer frames or shorter runs")
+    return n
+
+
+@dataclass
 class LinkStats:
     bit_errors: int
     symbol_errors: int
@@ -115,6 +178,7 @@ class LinkStats:
     clip_db: Optional[float] = None
     clipped_samples: Optional[int] = None  # samples whose |x|^2 exceeded the threshold
     clip_samples: Optional[int] = None     # samples examined: N per OFDM symbol
+    frames: Optional[FrameStats] = None    # run(..., frame_symbols=F)
 
 
 def default_papr_edges_db() -> np.ndarray:
@@ -360,12 +424,18 @@ class LinkEngine:
             B.check(self._lib.ofdm_tx_clip(*args, float(self.clip_a2), B.ptr(clip_counters)))
 
     def rx(self, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits_d, sym0, n_sym,
-           n_valid, counters, z_out=None, z_keep=0, profile=None):
-        """ofdm_rx, or with a profile record (device int64 [5][N]) ofdm_rx_profile."""
+           n_valid, counters, z_out=None, z_keep=0, profile=None, frames=None, frame_symbols=None):
+        """ofdm_rx, or with a profile record (device int64 [5][N]) ofdm_rx_profile, or with a frame
+        record (``frames``: device int64 [n_frames][2] of the whole run, ``frame_symbols`` OFDM symbols
+        per frame) ofdm_rx_frames."""
         args = (self.plan.handle, stream, B.ptr(y), B.ptr(nr), B.ptr(ni), int(seed), B.ptr(stats),
                 int(total_samples), float(snr_db), int(noise_on), B.ptr(bits_d), int(sym0), int(n_sym),
                 int(n_valid), B.ptr(counters), B.ptr(z_out), int(z_keep))
-        if profile is None:
+        if frames is not None:
+            if profile is not None:
+                raise ValueError("rx: a profile and a frame record together have no kernel (PROF x FRAMES is not built)")
+            B.check(self._lib.ofdm_rx_frames(*args, int(frame_symbols), int(frames.shape[0]), B.ptr(frames)))
+        elif profile is None:
             B.check(self._lib.ofdm_rx(*args))
         else:
             B.check(self._lib.ofdm_rx_profile(*args, B.ptr(profile)))
@@ -472,14 +542,15 @@ class LinkEngine:
 
     def _route_fused(self, fused: Optional[bool], *, philox: bool, tap: bool, profile: bool, whole: bool) -> bool:
         """The route of a run: ``fused`` None takes the fused one when the plan has a fused form, the
-        streams are Philox, there is no received-symbol tap, no profile and every bit is compared;
-        False forces the two-kernel path; True raises where no fused form exists."""
+        streams are Philox, there is no received-symbol tap, no profile (a frame record counts as one:
+        k_link has neither) and every bit is compared; False forces the two-kernel path; True raises
+        where no fused form exists."""
         clip = self.clip_a2 is not None  # (asked first: a clipped engine never probes the library)
         can = not clip and self.has_fused and philox and not tap and not profile and whole
         if fused and not can:
             raise ValueError("no fused form for this run: ofdm_link takes a complex128 N = 1024 fixed 64-QAM "
                              "cyclic-prefix OFDM plan over a flat channel without equaliser, Philox streams, "
-                             "no received-symbol tap, no profile and every bit compared, and no clip level "
+                             "no received-symbol tap, no profile or frame record and every bit compared, and no clip level "
                              "(clip_db: the limiter is not built into k_link)")
         return can if fused is None else bool(fused)
 
@@ -596,7 +667,8 @@ class LinkEngine:
                   normals: Optional[tuple] = None, seed: int = 0, noise_on: bool = True, keep_symbols: int = 0,
                   group=None, y_budget: int = DEFAULT_Y_BUDGET, batch: Optional[int] = None,
                   n_valid_bits: Optional[int] = None, events: Optional[list] = None,
-                  profile: bool = False, fused: Optional[bool] = None) -> "PendingLink":
+                  profile: bool = False, fused: Optional[bool] = None,
+                  frame_symbols: Optional[int] = None) -> "PendingLink":
         """Enqueue global OFDM symbols [0, n_sym) (this rank's shard when ``group`` is set) on
         the current stream without waiting for them; :meth:`PendingLink.result` reads the
         counts back.  Back-to-back calls therefore keep the GPU busy while the host prepares
@@ -606,7 +678,8 @@ class LinkEngine:
         normals : (nr, ni) float64 arrays of length n_sym*(N+cp) (reference mode), or None
                   for Philox noise
         events  : if a list, (kernel, n_symbols, start, end) HIP events are appended around
-                  every ofdm_tx / ofdm_rx launch (recorded on the launch stream)
+                  every ofdm_tx / ofdm_rx launch (recorded on the launch stream); with frame_symbols the
+                  receiver's are named "ofdm_rx_frames"
         profile : accumulate the per-subcarrier record of the whole run (LinkStats.profile): bit and
                   symbol errors, error-vector power and clipped samples per subcarrier, summed on the
                   device in integers by every batch and, with a group, over the ranks -- exact, so
@@ -614,6 +687,16 @@ class LinkEngine:
                   shapes with Philox streams and keep_symbols = 0 run their throughput receiver with
                   the profile compiled in, every other run the generic receiver; run_pipelined takes
                   no profile.
+        frame_symbols : F: accumulate the per-frame error record of the whole run (LinkStats.frames):
+                  the bit and symbol errors of every frame of F consecutive global OFDM symbols, int64
+                  [ceil(n_sym / F)][2] behind the counters, from which come the frame error rate, the
+                  BER's standard error and the errors-per-frame histogram (:class:`FrameStats`).  Each
+                  batch and each rank adds its own symbols' counts -- integers, so a frame split over
+                  two batches or two ranks just sums and the record is the same for any batching and
+                  rank count.  ofdm_rx_frames: the complex128 bench shapes with Philox streams and
+                  keep_symbols = 0 run their throughput receiver with the record compiled in, every
+                  other run the generic receiver.  At most B.MAX_FRAMES frames; not together with
+                  ``profile``; the fused route has no record (None takes the two-kernel path).
         fused   : the route.  None: the fused one -- a power pass, then one ofdm_link launch that
                   transmits and receives every symbol of the shard in registers: no y buffer, no
                   batching -- when the plan has a fused form (has_fused), the streams are Philox
@@ -621,10 +704,16 @@ class LinkEngine:
                   statistics, bit for bit.  False: the two-kernel path.  True: ValueError where no
                   fused form exists.  Events: ("ofdm_tx", ...) for the power pass, ("ofdm_link", ...).
         """
+        n_frames = 0
+        if frame_symbols is not None:
+            if profile:
+                raise ValueError("profile=True together with frame_symbols: the receiver with both records "
+                                 "(PROF x FRAMES) is not built; run twice")
+            n_frames = frame_count(n_sym, frame_symbols)
         r = self._share(n_sym, group, n_valid_bits)
         dev, N = r.dev, self.n_fft
         use_link = self._route_fused(fused, philox=bits is None and normals is None, tap=keep_symbols > 0,
-                                     profile=profile, whole=r.n_valid >= n_sym * self.bps)
+                                     profile=profile or n_frames > 0, whole=r.n_valid >= n_sym * self.bps)
 
         bits_d = None
         if bits is not None:
@@ -638,19 +727,24 @@ class LinkEngine:
             ni_d = self.upload(np.asarray(normals[1], np.float64))
 
         stats = new_stats(dev)
-        # the counters, and behind them the clip record and the profile record: one buffer, one all-reduce
+        # the counters, and behind them the clip record and the profile or frame record: one buffer, one
+        # all-reduce (every rank adds its own symbols' counts into the whole run's frame record)
         nclip = 0 if self.clip_a2 is None else 2
-        acc = torch.zeros(2 + nclip + (B.PROFILE_ROWS * N if profile else 0), dtype=torch.int64, device=dev)
+        acc = torch.zeros(2 + nclip + (B.PROFILE_ROWS * N if profile else 0) + 2 * n_frames, dtype=torch.int64,
+                          device=dev)
         counters = acc[:2]
         clip = acc[2:4] if nclip else None
         prof = acc[2 + nclip:].view(B.PROFILE_ROWS, N) if profile else None
         pkw = {"profile": prof} if profile else {}  # (rx without a profile is called as before)
+        frec = acc[2 + nclip:].view(n_frames, 2) if n_frames else None
+        if n_frames:  # (and without a frame record)
+            pkw = {"frames": frec, "frame_symbols": int(frame_symbols)}
         keep = min(keep_symbols, r.mine)
         z_out = torch.empty((keep, N), dtype=self.cdtype, device=dev) if keep else None
 
         def receive(y, sym0, n, resident):
             zk = keep if sym0 == r.lo else 0  # the tap: the shard's first symbols, so its first batch
-            self._timed(events if resident else None, "ofdm_rx", n, lambda: self.rx(
+            self._timed(events if resident else None, "ofdm_rx_frames" if n_frames else "ofdm_rx", n, lambda: self.rx(
                 r.stream, y, nr_d, ni_d, seed, stats, r.samples, snr_db, noise_on, bits_d, sym0, n, r.n_valid,
                 counters, z_out if zk else None, zk, **pkw))
 
@@ -661,7 +755,8 @@ class LinkEngine:
         done, work = self._schedule(r, seed, bits_d, stats, receive, acc, group=group, y_budget=y_budget,
                                     batch=batch, events=events, link=link if use_link else None, clip=clip)
         return PendingLink(n_sym, r.samples, stats, counters, z_out, done, work, prof,
-                           self.bits_per_subcarrier if profile else None, clip=clip, clip_db=self.clip_db)
+                           self.bits_per_subcarrier if profile else None, clip=clip, clip_db=self.clip_db,
+                           frames=frec, frame_info=(int(frame_symbols), self.bps, r.n_valid) if n_frames else None)
 
     # ------------------------------------------------------------------ one-pass SNR sweep
     def run_sweep(self, n_sym: int, snr_dbs, **kw) -> list:
@@ -671,7 +766,8 @@ class LinkEngine:
 
     def run_sweep_async(self, n_sym: int, snr_dbs, *, seed: int = 0, group=None,
                         y_budget: int = DEFAULT_Y_BUDGET, batch: Optional[int] = None,
-                        n_valid_bits: Optional[int] = None, events: Optional[list] = None) -> "PendingSweep":
+                        n_valid_bits: Optional[int] = None, events: Optional[list] = None,
+                        frame_symbols: Optional[int] = None) -> "PendingSweep":
         """Throughput-mode (Philox) runs of global OFDM symbols [0, n_sym) at every SNR of
         ``snr_dbs`` with one seed, from one transmit: point k is ``run(n_sym, snr_dbs[k], seed=seed)``
         -- the same bits, noise words, sigma and per-sample arithmetic, so in complex128 the same
@@ -683,8 +779,12 @@ class LinkEngine:
         longer than B.MAX_SWEEP_POINTS is split into several receiver launches over the same y.  The
         counts do not depend on the batching, the rank count, the order of the list or how it is split.
 
-        Not taken: caller bits or normals, orders above 256, a profile, a received-symbol tap, and
-        a plan per point (adaptive loading re-derived per SNR)."""
+        Not taken: caller bits or normals, orders above 256, a profile, a frame record
+        (``frame_symbols``: ValueError), a received-symbol tap, and a plan per point (adaptive loading
+        re-derived per SNR)."""
+        if frame_symbols is not None:
+            raise ValueError("run_sweep with frame_symbols: the sweep receiver keeps no frame record "
+                             "(frames inside k_rx_sweep are not built); use run per point")
         snrs = [float(q) for q in snr_dbs]
         if not snrs:
             raise ValueError("run_sweep needs at least one SNR point")
@@ -722,7 +822,7 @@ class LinkEngine:
 
     def run_pipelined(self, n_sym: int, snr_db, seeds, *, group=None,
                       events: Optional[list] = None, y_budget: int = DEFAULT_Y_BUDGET, lanes: int = 1,
-                      fused: Optional[bool] = None) -> list:
+                      fused: Optional[bool] = None, frame_symbols: Optional[int] = None) -> list:
         """Independent throughput-mode runs (one per seed) of global OFDM symbols [0, n_sym),
         software-pipelined across runs: run k+1's TX is enqueued before run k's RX, so with
         several ranks the statistics exchange of run k (the one collective on a run's
@@ -746,6 +846,9 @@ class LinkEngine:
         if self.clip_a2 is not None:
             raise ValueError("run_pipelined on an engine with clip_db: the pipelined schedule carries no clip "
                              "record; use run_async or run_sweep")
+        if frame_symbols is not None:
+            raise ValueError("run_pipelined with frame_symbols: the pipelined schedule carries no frame record; "
+                             "use run_async")
         seeds = list(seeds)
         snrs = list(snr_db) if isinstance(snr_db, (list, tuple, np.ndarray)) else [snr_db] * len(seeds)
         if len(snrs) != len(seeds):
@@ -842,9 +945,11 @@ class PendingLink(_Pending):
     """Device-side results of one :meth:`LinkEngine.run_async` call."""
 
     def __init__(self, n_sym, samples, stats, counters, z_out, done=None, work=None, profile=None,
-                 bits_per_subcarrier=None, clip=None, clip_db=None):
+                 bits_per_subcarrier=None, clip=None, clip_db=None, frames=None, frame_info=None):
         self.n_sym, self.samples = n_sym, samples
         self.clip, self.clip_db = clip, clip_db
+        # the run's frame record (device int64 [n_frames][2]) and (F, bits per OFDM symbol, bits compared)
+        self.frames, self.frame_info = frames, frame_info
         self.stats, self.counters, self.z_out = stats, counters, z_out
         self.profile, self.bits_per_subcarrier = profile, bits_per_subcarrier
         self.done, self.work = done, work
@@ -861,8 +966,15 @@ class PendingLink(_Pending):
                                      error_power=profile_power(rec), error_power_fx=rec[2:4].copy(),
                                      n_symbols=self.n_sym,
                                      bits_per_subcarrier=self.bits_per_subcarrier)
+        fr = None
+        if self.frames is not None:
+            F, bps, n_valid = self.frame_info
+            rec = self.frames.cpu().numpy().astype(np.int64)[:-(-self.n_sym // F)]  # (an empty run: no frame)
+            fr = FrameStats(frame_symbols=F, n_symbols=self.n_sym, bits_per_symbol=bps, bit_errors=rec[:, 0].copy(),
+                            symbol_errors=rec[:, 1].copy(), n_valid_bits=n_valid)
         return LinkStats(bit_errors=int(cnt[0]), symbol_errors=int(cnt[1]),
-                         received=None if z is None else z.cpu().numpy().reshape(-1), profile=prof, **shared)
+                         received=None if z is None else z.cpu().numpy().reshape(-1), profile=prof, frames=fr,
+                         **shared)
 
 
 class PendingSweep(_Pending):

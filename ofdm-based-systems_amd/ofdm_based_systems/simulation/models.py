@@ -140,8 +140,18 @@ class Simulation:
         papr_ccdf: bool = False,
         papr_edges_db=None,
         clip_db: Optional[float] = None,
+        frame_symbols: Optional[int] = None,
     ):
-        """clip_db: limit the envelope of the transmitted samples at ``clip_db`` dB above the nominal
+        """frame_symbols: F: also return when the errors fall -- the bit errors of every frame of F
+        consecutive OFDM symbols, accumulated on the GPU (engine.FrameStats, ``LinkEngine.run(
+        frame_symbols=F)``, ofdm_rx_frames): the keys ``frame_symbols``, ``num_frames`` (full frames),
+        ``frame_errors``, ``frame_error_rate``, ``ber_std_error`` (None with fewer than two full frames
+        or when a trailing partial byte is not compared) and ``bit_errors_per_frame`` (a list, a
+        trailing partial frame included).  Without it the result dict is unchanged.  Needs the fused
+        path (the built-in modulators, prefixes and constellations); not combined with
+        ``subcarrier_profile`` or ``run_sweep``.
+
+        clip_db: limit the envelope of the transmitted samples at ``clip_db`` dB above the nominal
         mean sample power (a soft limiter directly after the IFFT -- for SC-OFDM on the mapped points --
         before the guard and the channel; ``LinkEngine(clip_db=...)``, ofdm_tx_clip).  Every reported
         figure then describes the clipped stream, and the result gains ``clip_db``, ``clipped_samples``
@@ -197,6 +207,7 @@ class Simulation:
         self.papr_ccdf = papr_ccdf
         self.papr_edges_db = papr_edges_db
         self.clip_db = clip_db
+        self.frame_symbols = frame_symbols
 
     def _log(self, message: str) -> None:
         if self.verbose:
@@ -220,7 +231,7 @@ class Simulation:
             except Exception as e:  # noqa: BLE001
                 raise ValueError(f"Failed to load channel model from {path}: {e}")
         extra = {"rng_mode": s.rng_mode, "seed": s.seed, "precision": s.precision,
-                 "batch_symbols": s.batch_symbols, "clip_db": s.clip_db}
+                 "batch_symbols": s.batch_symbols, "clip_db": s.clip_db, "frame_symbols": s.frame_symbols}
         return [
             cls(num_bits=s.num_bits, num_symbols=s.num_symbols, num_subcarriers=s.num_bands,
                 constellation_order=s.constellation_order, constellation_scheme=s.constellation_type,
@@ -308,17 +319,16 @@ class Simulation:
         s0 = sims[0]
         if s0.rng_mode != "philox":
             raise ValueError("run_sweep needs rng_mode='philox' (the sweep receiver generates its streams)")
-        builtin = (cls.MODULATOR_SCHEME_MAPPERS.get(s0.modulator_type) in (OFDMModulator, SingleCarrierOFDMModulator)
-                   and cls.PREFIX_SCHEME_MAPPERS.get(s0.prefix_scheme) in (
-                       CyclicPrefixScheme, ZeroPaddingPrefixScheme, NoPrefixScheme)
-                   and cls.CONSTELLATION_SCHEME_MAPPERS.get(s0.constellation_scheme) in (
-                       QAMConstellationMapper, PSKConstellationMapper)
+        builtin = (s0._builtin_strategies()
                    and cls.NOISE_SCHEME_MAPPERS.get(s0.noise_scheme, AWGNoiseModel) is AWGNoiseModel)
         if s0.adaptive_modulation_mode != AdaptiveModulationMode.FIXED or not builtin:
             raise ValueError("run_sweep needs FIXED mode with the built-in modulators, prefixes, constellations "
                              "and AWGN (adaptive loading is a different plan per SNR)")
         if s0.received_symbols_keep != 0 or s0.subcarrier_profile:
             raise ValueError("run_sweep needs received_symbols_keep=0 and no subcarrier_profile")
+        if s0.frame_symbols is not None:
+            raise ValueError("run_sweep with frame_symbols: the sweep receiver keeps no frame record; run the "
+                             "simulations one by one")
 
         swept: List[Any] = []  # the engine sweep's LinkStats, filled by the first simulation
 
@@ -339,17 +349,32 @@ class Simulation:
         orders above 256 (``orders``: the adaptive loading's, once known)."""
         if self.papr_ccdf:
             raise ValueError("papr_ccdf with clip_db: the PAPR histogram of a clipped stream is not built")
-        if (self.MODULATOR_SCHEME_MAPPERS.get(self.modulator_type, OFDMModulator) not in (
-                OFDMModulator, SingleCarrierOFDMModulator)
-                or self.PREFIX_SCHEME_MAPPERS.get(self.prefix_scheme, NoPrefixScheme) not in (
-                    CyclicPrefixScheme, ZeroPaddingPrefixScheme, NoPrefixScheme)
-                or self.CONSTELLATION_SCHEME_MAPPERS.get(self.constellation_scheme, QAMConstellationMapper) not in (
-                    QAMConstellationMapper, PSKConstellationMapper)):
+        if not self._builtin_strategies():
             raise ValueError("clip_db needs the built-in modulators, prefixes and constellations")
         top = (self.constellation_order if self.adaptive_modulation_mode == AdaptiveModulationMode.FIXED
                else 0 if orders is None else int(np.max(orders, initial=0)))
         if top > 256:
             raise ValueError(f"clip_db takes constellation orders up to 256, got {top}")
+
+    def _builtin_strategies(self) -> bool:
+        """Whether the modulator, prefix and constellation are the built-in classes (the fused path's)."""
+        return (self.MODULATOR_SCHEME_MAPPERS.get(self.modulator_type, OFDMModulator) in (
+                    OFDMModulator, SingleCarrierOFDMModulator)
+                and self.PREFIX_SCHEME_MAPPERS.get(self.prefix_scheme, NoPrefixScheme) in (
+                    CyclicPrefixScheme, ZeroPaddingPrefixScheme, NoPrefixScheme)
+                and self.CONSTELLATION_SCHEME_MAPPERS.get(self.constellation_scheme, QAMConstellationMapper) in (
+                    QAMConstellationMapper, PSKConstellationMapper))
+
+    def _check_frames(self) -> None:
+        """What a frame record is not combined with, refused before the run: user-supplied strategy
+        classes (the composed path keeps no record), the per-subcarrier profile, a bad frame length."""
+        F = self.frame_symbols
+        if isinstance(F, bool) or not isinstance(F, (int, np.integer)) or F < 1:
+            raise ValueError(f"frame_symbols = {F!r} is not a positive number of OFDM symbols")
+        if not self._builtin_strategies():
+            raise ValueError("frame_symbols needs the built-in modulators, prefixes and constellations")
+        if self.subcarrier_profile:
+            raise ValueError("frame_symbols with subcarrier_profile: the receiver with both records is not built")
 
     def _run(self, link=None) -> Dict[str, Any]:
         """run(); ``link`` (run_sweep): a callable (make_engine, n_sym, seed, valid_bits) -> LinkStats
@@ -357,6 +382,8 @@ class Simulation:
         results: Dict[str, Any] = {}
         if self.clip_db is not None:
             self._check_clip()  # (before anything is launched)
+        if self.frame_symbols is not None:
+            self._check_frames()
         sp = SerialToParallelConverter()
         noise_model = self.NOISE_SCHEME_MAPPERS.get(self.noise_scheme, AWGNoiseModel)()
         h_raw = np.asarray(DEFAULT_CHANNEL if self.channel_impulse_response is None
@@ -472,6 +499,8 @@ class Simulation:
             raise ValueError("rng_mode='philox' needs the built-in modulators, prefixes and constellations")
         if not fused and self.subcarrier_profile:
             raise ValueError("subcarrier_profile needs the built-in modulators, prefixes and constellations")
+        if not fused and self.frame_symbols is not None:  # (_check_frames saw the strategy classes)
+            raise ValueError("frame_symbols needs the fused path (channel order and prefix within n_fft)")
         if not fused and self.papr_ccdf:
             raise ValueError("papr_ccdf needs the built-in modulators, prefixes and constellations")
         if not fused and self.clip_db is not None:
@@ -502,7 +531,8 @@ class Simulation:
                 st = eng.run(n_ofdm_syms, self.snr_db, bits=tx_bytes, normals=normals, seed=seed,
                              noise_on=noise_on, keep_symbols=self.received_symbols_keep,
                              group=self.process_group, batch=self.batch_symbols,
-                             n_valid_bits=valid_bits, profile=self.subcarrier_profile)
+                             n_valid_bits=valid_bits, profile=self.subcarrier_profile,
+                             **({} if self.frame_symbols is None else {"frame_symbols": self.frame_symbols}))
             if self.papr_ccdf:
                 # the per-symbol PAPR distribution of the stream just transmitted: the same plan, seed
                 # and (reference mode) the run's own bits
@@ -536,6 +566,16 @@ class Simulation:
                 "symbol_errors_per_subcarrier": profile.symbol_errors,
                 "error_power_per_subcarrier": profile.error_power,
                 "mer_db_per_subcarrier": profile.mer_db,
+            })
+        if self.frame_symbols is not None:
+            fr = st.frames
+            results.update({
+                "frame_symbols": fr.frame_symbols,
+                "num_frames": fr.n_full,
+                "frame_errors": fr.frame_errors,
+                "frame_error_rate": fr.fer,
+                "ber_std_error": fr.ber_stderr,
+                "bit_errors_per_frame": fr.bit_errors.tolist(),
             })
         if self.clip_db is not None:
             results.update({
