@@ -49,6 +49,12 @@
 // SCREEN = none, Two and Noise compile to the instructions they had with a copy each
 // (profiles/link_refactor_kernel_audit.txt); the symbol loop stays inline for the same reason -- a lambda
 // or a function around the screened symbol, even one never called, moves all four kernels' registers.
+//
+// The screens also share the wave sum of the norm (wave_sum_f32: DPP and lane swaps, no LDS), so that the
+// sparse form's delta, and with it the symbols it redoes, stay the noise screen's.  The sparse form alone has
+// the max3 maxima (the quad test and the margin, max_abs2 / max_abs3) and its own copy of the generator step
+// for the screened symbol's noise (ScreenMwc): Two and Noise differ from their earlier code by the sum only,
+// none not at all (profiles/link_trim_kernel_audit.txt).
 #pragma once
 
 #include "ofdm_kernels_inst.hpp"
@@ -64,6 +70,15 @@ namespace ofdm {
 #endif
 #ifndef OFDM_LINK_WAVES
 #define OFDM_LINK_WAVES 3
+#endif
+// OFDM_LINK_NOREDO (ablation builds only, with OFDM_LINK_BLOCK=1024 and OFDM_LINK_WAVES=4): the sparse form
+// without its complex128 redo and that redo's tables (the double twiddles and LUT staged through the rows,
+// no ntab64) -- the ceiling of a float32-only screen kernel.  A timing build: an undecided symbol is
+// counted from its float32 words, and the other instantiations are not meant to be launched from it.
+#if OFDM_ABLATION && defined(OFDM_LINK_NOREDO)
+constexpr bool link_noredo(int screen) { return screen == kLinkScreenSparse; }
+#else
+constexpr bool link_noredo(int) { return false; }
 #endif
 
 // (k_link's SCREEN -- kLinkScreenNone, Two, Noise, Sparse -- is ofdm_launch.hpp's: the ABI names one)
@@ -87,7 +102,7 @@ __host__ __device__ __forceinline__ constexpr LinkLds<R> link_carve(CV& cv) {
     // (PADN complex64 take what PADN doubles take: the float32 transforms exchange through the same row)
     m.rowmem = cv.template take<unsigned char>((size_t)G::SPB * G::PADN * sizeof(R));
     m.redc = cv.template take<unsigned long long>(OFDM_LINK_BLOCK / 64);
-    m.tt = cv.template take<cpx<R>>(2 * tt_size(LOGN));
+    m.tt = cv.template take<cpx<R>>(link_noredo(SCREEN) ? 0 : 2 * tt_size(LOGN));
     m.tt32 = cv.template take<cpx<float>>(SCREEN == kLinkScreenTwo ? 2 * tt_size(LOGN) : SCREEN ? tt_size(LOGN) : 0);
     m.lut32 = cv.template take<cpx<float>>(SCREEN ? (1 << FB) : 0);
     return m;
@@ -116,6 +131,21 @@ constexpr double kScreenSlicerU = 40.0;
 // share 1 - exp(-0.35) = 0.30 of the symbols redone; the screen pays below about 0.4)
 constexpr double kScreenMaxUndecided = 0.35;
 
+// The sparse form's largest moduli (the quad test's components, the margin's two axes): v_max_f32 / v_max3_f32
+// on the |.| source modifiers, one instruction per element.  fmaxf of two fabsf quiets each operand first (a
+// v_max_f32 |a|, |a| apiece); these return the same number for every input that is not a NaN, and drop a NaN
+// as fmaxf does -- the kernel says what becomes of a symbol with one.
+__device__ __forceinline__ float max_abs2(f32x2 a) {
+    float r;
+    asm("v_max_f32 %0, |%1|, |%2|" : "=v"(r) : "v"(a.x), "v"(a.y));
+    return r;
+}
+__device__ __forceinline__ float max_abs3(f32x2 a, float mx) {
+    float r;
+    asm("v_max3_f32 %0, |%1|, |%2|, %3" : "=v"(r) : "v"(a.x), "v"(a.y), "v"(mx));
+    return r;
+}
+
 // PermSlicer with the decision's margin: m = max(m, |y - round(y)|) over both axes of the four elements,
 // y the clamped level coordinate -- 1/2 - m is the distance to the nearest decision boundary (a clamped
 // end gives y = round(y): never near one).
@@ -128,6 +158,8 @@ struct ScreenSlicer : PermSlicer<FB> {
         const float is = (float)(a.inv_step * scale / (double)(P::SIDE - 1));
         this->mul = f32x2{is, is};
     }
+    // MAX3: the margin through max_abs3 (the sparse form; the other screens keep their instructions)
+    template <bool MAX3 = false>
     __device__ __forceinline__ uint32_t diff_margin(const cpx<float> (&z)[4], uint32_t txw, float& m) const {
         uint32_t li[4], lq[4];
 #pragma unroll
@@ -142,7 +174,8 @@ struct ScreenSlicer : PermSlicer<FB> {
             // scalar float (no lane of a packed value is reinterpreted)
             const float ri = __uint_as_float(li[j]) - 12582912.0f, rq = __uint_as_float(lq[j]) - 12582912.0f;
             const float ei = __builtin_fmaf(v.x, this->smax.x, -ri), eq = __builtin_fmaf(v.y, this->smax.x, -rq);
-            m = __builtin_fmaxf(m, __builtin_fmaxf(__builtin_fabsf(ei), __builtin_fabsf(eq)));
+            if constexpr (MAX3) m = max_abs3(f32x2{ei, eq}, m);
+            else m = __builtin_fmaxf(m, __builtin_fmaxf(__builtin_fabsf(ei), __builtin_fabsf(eq)));
         }
         const uint32_t si = __builtin_amdgcn_perm(__builtin_amdgcn_perm(li[3], li[2], 0x0c0c0400u),
                                                   __builtin_amdgcn_perm(li[1], li[0], 0x0c0c0400u), 0x05040100u);
@@ -264,6 +297,50 @@ struct AddPoint {
     __device__ __forceinline__ void operator()(I) const { xf[I::value].v += lut32[tb.template fixed<I::value>()].v; }
 };
 
+// The screens' wave sum of a float (the norm ||ghat||^2), the same bits in every lane, without LDS: four DPP
+// adds inside a row of 16 lanes (lane ^ 1, lane ^ 2, then the row's half and whole mirrors, every lane of a
+// quad and of a half row already holding the same partial sum), then the rows through v_permlane16_swap
+// and v_permlane32_swap of the value with itself -- where __shfl_xor is six ds_bpermute round trips.
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float wave_sum_f32(float v) {
+    v += dpp_f32<0xB1>(v);   // quad_perm:[1,0,3,2]
+    v += dpp_f32<0x4E>(v);   // quad_perm:[2,3,0,1]
+    v += dpp_f32<0x141>(v);  // row_half_mirror
+    v += dpp_f32<0x140>(v);  // row_mirror
+    const auto r16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = __uint_as_float(r16[0]) + __uint_as_float(r16[1]);  // rows 0 + 1 | rows 2 + 3
+    const auto r32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return __uint_as_float(r32[0]) + __uint_as_float(r32[1]);
+}
+
+// The sparse form's copy of the lane generator for the screened symbol's noise: Mwc64x's outputs, word for
+// word (tests/test_oracle_philox.py pins the stream), with the carry held zero-extended so that a step is
+// the v_mad_u64_u32 onto that pair and one v_lshrrev_b64 of the product -- where (x, c) in two words costs
+// two v_mov_b32 a step to rebuild the addend (c, 0).  The shared generator and every other kernel stay.
+struct ScreenMwc {
+    uint32_t x, q;
+    uint64_t cz;  // the carry c, its high word 0
+    __device__ __forceinline__ explicit ScreenMwc(const Mwc64x& g) : x(g.x), q(0), cz(g.c) {}
+    __device__ __forceinline__ uint32_t next() {
+        const uint32_t r = x ^ (uint32_t)cz;
+        const uint64_t v = (uint64_t)kMwcA * x + cz;
+        x = (uint32_t)v;
+        asm("v_lshrrev_b64 %0, 32, %1" : "=v"(cz) : "v"(v));
+        return r;
+    }
+    // Mwc64x::add_noise: the phase word before samples 0 mod 4, the radius word, one packed FMA
+    __device__ __forceinline__ void add_noise(f32x2& x0, const f32x2* ntab, int j) {
+        if ((j & 3) == 0) q = next();
+        const float r = noise_radius(next());
+        const uint32_t off = ((q >> (8 * (j & 3))) & (uint32_t)(kNoisePhases - 1)) * (uint32_t)sizeof(f32x2);
+        const f32x2 e = *(const f32x2*)((const unsigned char*)ntab + off);
+        x0 = __builtin_elementwise_fma(f32x2{r, r}, e, x0);
+    }
+};
+
 template <typename R, int LOGN, int FB, int SCREEN = kLinkScreenNone>
 __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkArgs la) {
     static_assert(sizeof(R) == 8 && FB > 1 && !(FB & 1), "complex128 fixed square QAM");
@@ -271,6 +348,7 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
     static_assert(!SCREEN || Geo<LOGN>::TPS == 64, "the screen's ballot and its redo are one wave's");
     constexpr bool NOISE_ALONE = SCREEN == kLinkScreenNoise || SCREEN == kLinkScreenSparse;
     constexpr bool SPARSE = SCREEN == kLinkScreenSparse;
+    constexpr bool NOREDO = link_noredo(SCREEN);
     constexpr int BLK = OFDM_LINK_BLOCK;
     using G = Geo<LOGN, BLK>;
     using C = cpx<R>;
@@ -283,7 +361,8 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
     __shared__ f64x2 ntab64[kNoisePhases];
     Carve cv(ofdm_smem);
     const LinkLds<R> lds = link_carve<R, LOGN, SCREEN, FB>(cv);
-    C* tt = lds.tt;
+    C* tt = NOREDO ? (C*)lds.rowmem : lds.tt;
+    C* const lutd = NOREDO ? tt + 2 * TTS : lut_s;
     AxisInfo* axis = lds.axis;
     unsigned long long* redc = lds.redc;
 
@@ -305,11 +384,11 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
         sigma_d = sqrt((p / a.snr_lin) / 2.0);
         power = p;
     }
-    build_noise_table(ntab, sigma_d, ntab64);
+    build_noise_table(ntab, sigma_d, NOREDO ? nullptr : ntab64);
     st_tt.store(tt);
     // the 1/sqrt(N) of ifft(norm="ortho") and the channel tap folded into the LUT (as k_tx, FOLD_H0)
     const R lut_scale = (R)cm.scale;
-    st_lut.store(lut_s, [&](const C& v) { return cscale(cmul(hf, v), lut_scale); });
+    st_lut.store(lutd, [&](const C& v) { return cscale(cmul(hf, v), lut_scale); });
     st_ax.store((Dwords<AxisInfo>*)axis);
     __syncthreads();
 
@@ -339,7 +418,7 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
         for (int i = threadIdx.x; i < (NOISE_ALONE ? 1 : 2) * TTS; i += BLK) tt32[i] = mk<float>((float)tt[i].re, (float)tt[i].im);
         double amax = 0;
         for (int i = 0; i < (1 << FB); ++i) {
-            const C v = lut_s[i];
+            const C v = lutd[i];
             amax = fmax(amax, v.re * v.re + v.im * v.im);
             if (i == (int)threadIdx.x) lut32[i] = mk<float>(POINT * (float)v.re, POINT * (float)v.im);
         }
@@ -414,8 +493,14 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
 #pragma unroll
                         for (int i = 0; i < E; ++i) xf[i] = mk<float>(0.f, 0.f);
                         if (noise) {
+                            if constexpr (SPARSE) {
+                                ScreenMwc g(tb.g);
 #pragma unroll
-                            for (int i = 0; i < E; ++i) tb.g.add_noise(xf[i].v, ntab, i);
+                                for (int i = 0; i < E; ++i) g.add_noise(xf[i].v, ntab, i);
+                            } else {
+#pragma unroll
+                                for (int i = 0; i < E; ++i) tb.g.add_noise(xf[i].v, ntab, i);
+                            }
                             fft_sym<float, LOGN, false, FB>(xf, rowf, tt32, tt32, t);
 #pragma unroll
                             for (int i = 0; i < E; ++i) acc = __builtin_elementwise_fma(xf[i].v, xf[i].v, acc);
@@ -428,9 +513,7 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
 #endif
                         if (!SPARSE || !sparse) static_for<0, E>(Add{xf, lut32, tb});
                     }
-                    float n2 = acc.x + acc.y;
-#pragma unroll
-                    for (int off = 32; off > 0; off >>= 1) n2 += __shfl_xor(n2, off, 64);
+                    const float n2 = wave_sum_f32(acc.x + acc.y);
                     // (a delta of 1/2 or more, or a norm that is not finite: nothing is decisive)
                     const float delta = __builtin_fmaf(cz, __builtin_amdgcn_sqrtf(n2), c0);  // (v_sqrt_f32: 1 ulp)
                     const float thr = delta < 0.5f ? 0.5f - delta : -1.0f;
@@ -442,7 +525,7 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
                         CF z[4];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) z[j] = xf[4 * q + j];
-                        const uint32_t d = fslicer.diff_margin(z, lane_word(tb.lane, q), m);
+                        const uint32_t d = fslicer.template diff_margin<SPARSE>(z, lane_word(tb.lane, q), m);
                         bes += __popc(d);
                         ses += PermSlicer<FB>::nonzero_bytes(d);
                     };
@@ -453,11 +536,11 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
                             const float T = (thr - e0) * inv_lvl;
                             static_for<0, E / 4>([&](auto Q) {
                                 constexpr int q = Q;
-                                float mx = 0.f;
+                                // (a component that is not finite may drop out of mx, but it has made n2 not
+                                // finite, thr = -1 and T < 0 <= mx: every quad is sliced, as before)
+                                float mx = max_abs2(xf[4 * q].v);
 #pragma unroll
-                                for (int j = 0; j < 4; ++j)
-                                    mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(xf[4 * q + j].v.x),
-                                                                             __builtin_fabsf(xf[4 * q + j].v.y)));
+                                for (int j = 1; j < 4; ++j) mx = max_abs3(xf[4 * q + j].v, mx);
                                 if (__ballot(!(mx <= T)) != 0) {  // (wave-uniform)
                                     static_for<4 * q, 4 * q + 4>(Add{xf, lut32, tb});
                                     slice(Q);
@@ -474,6 +557,10 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
 #endif
                     if (!SPARSE || !sparse) static_for<0, E / 4>(slice);
                     redo = __ballot(!(m <= thr)) != 0;  // one undecided axis: the wave redoes the symbol
+                    if constexpr (NOREDO) {  // (counted as redone, taken from its float32 words)
+                        be += redo ? bes : 0u;
+                        se += redo ? ses : 0u;
+                    }
                     if (!redo) {
                         be += bes;
                         se += ses;
@@ -486,7 +573,7 @@ __global__ __launch_bounds__(OFDM_LINK_BLOCK, OFDM_LINK_WAVES) void k_link(LinkA
                 }
             }
         }
-        if (!SCREEN || redo) {
+        if ((!SCREEN || redo) && !NOREDO) {
             // the lane block: bits for both halves, the generator continuing into the lane's noise
             TxBits<FB, TPS> tb;
             tb.load(cm, sg, t, nullptr, active);
