@@ -314,6 +314,51 @@ int ofdm_rx_frames(ofdm_plan_t plan, void* stream, const void* y, const double* 
                    int64_t n_valid_bits, uint64_t* counters, void* z_out, int64_t z_keep,
                    int64_t frame_len, int64_t n_frames, uint64_t* frames);
 
+/* Bins per axis of ofdm_rx_density's grid at most: the kernel's histogram is G * G 32-bit bins in LDS,
+ * 64 KB at 128. */
+#define OFDM_MAX_DENSITY_BINS 128
+
+/*
+ * ofdm_rx with a constellation-density record of the run (an entry point added to ABI 6: nothing of the
+ * version's existing interface changes, so the number stands): where the received points fall in the
+ * I/Q plane, every equalised point of the call binned into a G x G grid over a square.
+ *
+ * The value binned: for every OFDM symbol of the call and every active element, the equalised symbol v
+ * -- the value the received-symbol tap (z_out) stores for that element, in the plan's precision.  The
+ * throughput receivers, which fold the MMSE scale and 1/sqrt(N) into the slicer, bin the point
+ * ofdm_rx_profile forms for its error vector (the unscaled equaliser output times that scale).  An
+ * adaptive plan's order-0 subcarriers carry no point and are not binned; SC-OFDM and zero padding bin
+ * what their tap would store.
+ * Subcarrier range [k_lo, k_hi): only elements whose subcarrier index k lies in it are binned (the whole
+ * symbol: 0, N); elements outside it count nowhere.
+ * The grid: G = bins per axis, 1 <= G <= OFDM_MAX_DENSITY_BINS = 128, given by two doubles the host forms in double from an
+ * extent L: lo = -L and inv_w = G / (2 L).  The library never sees L.
+ * The index is taken in double in both precisions (a complex64 component is widened first, which is
+ * exact).  Per axis t = (c - lo) * inv_w, one rounded subtraction and one rounded multiplication, never
+ * contracted into an FMA: the same two IEEE operations on the same c give the same t anywhere.  The
+ * point is inside iff 0 <= t < G on both axes (a NaN or an infinity fails the comparison: a ZF point on
+ * a null bin is outside).  Inside: hist[iy * G + ix] += 1, ix = (int) t of the real part, iy of the
+ * imaginary part.  Otherwise hist[G * G] += 1, the `outside` count.
+ * hist: device uint64[G * G + 1], accumulated and never zeroed by the library.  Integers only; a point's
+ * v is a function of (plan, seed or caller streams, symbol) in a given kernel form, so the record is the
+ * same for any grid, batching, split of a run over calls (sym0) or ranks, as long as every call of the
+ * run takes the same form.
+ * OFDM_E_INVALID, before any launch: what ofdm_rx refuses; hist == NULL; bins outside [1, 128]; lo or
+ *   inv_w not finite, or inv_w <= 0; a range that is not 0 <= k_lo < k_hi <= N; a layout that, with the
+ *   histogram (4 G^2 bytes), does not fit the 160 KB of LDS of a compute unit.  n_sym = 0: an empty call.
+ * Kernels (k_rx_dens), routed as ofdm_rx_profile's: the complex128 bench shapes (cyclic-prefix OFDM;
+ * 64-QAM at N = 1024, adaptive square-QAM loading at N = 2048, 256-QAM at N = 4096) with throughput
+ * streams (bits == NULL, nr == NULL) and z_out == NULL run their throughput receiver's form; every other
+ * call the generic kernel's -- a call with z_out != NULL also when z_keep is 0, so that a run with a tap
+ * can hold one form over all its calls.  Everything else -- arguments, counters, z_out / z_keep -- is
+ * ofdm_rx's.
+ */
+int ofdm_rx_density(ofdm_plan_t plan, void* stream, const void* y, const double* nr, const double* ni,
+                    uint64_t seed, const ofdm_stats* stats, int64_t total_samples, double snr_db,
+                    int32_t noise_on, const uint8_t* bits, int64_t sym0, int64_t n_sym,
+                    int64_t n_valid_bits, uint64_t* counters, void* z_out, int64_t z_keep,
+                    double lo, double inv_w, int32_t bins, int32_t k_lo, int32_t k_hi, uint64_t* hist);
+
 /*
  * The one-pass SNR sweep receiver (an entry point added to ABI 6: nothing of the version's existing
  * interface changes, so the number stands): ofdm_rx of the same channel samples at n_snr SNR points in

@@ -270,8 +270,11 @@ hipError_t with_prec(ofdm_plan_t p, F f) {
 }
 
 // The generic fused kernel's LDS layout for this shape exceeds a CU's (launcher: kLdsOverflow).
+// (lds_extra: what the entry point being served adds to the receiver's layout, named in the message --
+// ofdm_rx_density's histogram, set around its launch -- and empty otherwise)
+thread_local std::string lds_extra;
 int lds_overflow(ofdm_plan_t p, const char* who) {
-    return fail(OFDM_E_INVALID, std::string(who) + ": the shape does not fit the LDS of a compute unit (n_fft " +
+    return fail(OFDM_E_INVALID, std::string(who) + ": the shape" + lds_extra + " does not fit the LDS of a compute unit (n_fft " +
                                     std::to_string(p->n) + ", " + (p->prec == OFDM_F32 ? "complex64" : "complex128") +
                                     ", prefix " + std::to_string(p->cp) + ", " + std::to_string(p->L) + " taps, " +
                                     std::to_string(p->bps) + " bits per OFDM symbol, LUT pool " +
@@ -919,12 +922,34 @@ static int frames_ok(const char* who, const RxFrames& fr, int64_t sym0, int64_t 
     }
     return (int)OFDM_OK;
 }
-// ofdm_rx, ofdm_rx_profile and ofdm_rx_frames (who; profile: the record, or null; fr: the frame record, or
-// null -- without either, ofdm_rx, whose checks, arguments and launch are then what they were)
+// ofdm_rx_density's record and grid (ofdm_hip.h)
+struct RxDens {
+    double lo, inv_w;
+    int32_t bins, k_lo, k_hi;
+    uint64_t* hist;
+};
+// The density record's own refusals, made before anything else is looked at (n_fft: the plan's, or 0
+// without a plan, which rx_args then refuses)
+static int dens_ok(const char* who, const RxDens& d, int n_fft) {
+    const auto no = [&](const std::string& why) { return fail(OFDM_E_INVALID, std::string(who) + ": " + why); };
+    if (!d.hist) return no("needs a density record");
+    if (d.bins < 1 || d.bins > OFDM_MAX_DENSITY_BINS)
+        return no("bins " + std::to_string(d.bins) + " is not in [1, " + std::to_string(OFDM_MAX_DENSITY_BINS) + "]");
+    if (!std::isfinite(d.lo)) return no("lo is not finite");
+    if (!std::isfinite(d.inv_w) || !(d.inv_w > 0)) return no("inv_w is not a finite positive bin rate");
+    if (d.k_lo < 0 || d.k_lo >= d.k_hi || (n_fft > 0 && d.k_hi > n_fft))
+        return no("the subcarrier range [" + std::to_string(d.k_lo) + ", " + std::to_string(d.k_hi) +
+                  ") is not 0 <= k_lo < k_hi <= n_fft" + (n_fft > 0 ? " = " + std::to_string(n_fft) : std::string()));
+    return (int)OFDM_OK;
+}
+// ofdm_rx, ofdm_rx_profile, ofdm_rx_frames and ofdm_rx_density (who; profile: the record, or null; fr: the
+// frame record, or null; dn: the density record, or null -- without any, ofdm_rx, whose checks, arguments
+// and launch are then what they were)
 static int rx_call(const char* who, ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni,
                    uint64_t seed, const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on,
                    const uint8_t* bits, int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters,
-                   void* z_out, int64_t z_keep, int64_t* profile, const RxFrames* fr = nullptr) {
+                   void* z_out, int64_t z_keep, int64_t* profile, const RxFrames* fr = nullptr,
+                   const RxDens* dn = nullptr) {
     RxArgs a{};
     bool run;
     const int rc = rx_args(who, p, y, nr, ni, seed, stats, total_samples, noise_on, bits, sym0, n_sym, n_valid_bits,
@@ -947,6 +972,23 @@ static int rx_call(const char* who, ofdm_plan_t p, void* stream, const void* y, 
         return checked(who, p, with_prec(p, [&](auto r) {
             return launch_rx_frames<decltype(r)>(p->logn, a, ft, (hipStream_t)stream);
         }));
+    }
+    if (dn) {
+        RxDensTail d{};  // (flush: the launcher's, by its workgroup shape)
+        d.hist = (unsigned long long*)dn->hist;
+        d.lo = dn->lo;
+        d.inv_w = dn->inv_w;
+        d.bins = dn->bins;
+        d.k_lo = dn->k_lo;
+        d.k_hi = dn->k_hi;
+        // (a generic-form layout that does not fit with the histogram: named, nothing was launched)
+        lds_extra = " with its " + std::to_string(dn->bins) + " x " + std::to_string(dn->bins) +
+                    " density histogram (" + std::to_string(4 * dn->bins * dn->bins) + " bytes)";
+        const int rc = checked(who, p, with_prec(p, [&](auto r) {
+            return launch_rx_dens<decltype(r)>(p->logn, a, d, (hipStream_t)stream);
+        }));
+        lds_extra.clear();
+        return rc;
     }
     return checked(who, p, with_prec(p, [&](auto r) {
         using R = decltype(r);
@@ -979,6 +1021,17 @@ int ofdm_rx_frames(ofdm_plan_t p, void* stream, const void* y, const double* nr,
     if (const int rc = frames_ok("ofdm_rx_frames", fr, sym0, n_sym)) return rc;
     return rx_call("ofdm_rx_frames", p, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0,
                    n_sym, n_valid_bits, counters, z_out, z_keep, nullptr, &fr);
+}
+
+int ofdm_rx_density(ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni, uint64_t seed,
+                    const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on,
+                    const uint8_t* bits, int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters,
+                    void* z_out, int64_t z_keep, double lo, double inv_w, int32_t bins, int32_t k_lo, int32_t k_hi,
+                    uint64_t* hist) {
+    const RxDens dn{lo, inv_w, bins, k_lo, k_hi, hist};
+    if (const int rc = dens_ok("ofdm_rx_density", dn, p ? p->n : 0)) return rc;
+    return rx_call("ofdm_rx_density", p, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0,
+                   n_sym, n_valid_bits, counters, z_out, z_keep, nullptr, nullptr, &dn);
 }
 
 int ofdm_rx_sweep(ofdm_plan_t p, void* stream, const void* y, uint64_t seed, const ofdm_stats* stats,

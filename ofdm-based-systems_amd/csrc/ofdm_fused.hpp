@@ -1443,10 +1443,30 @@ __device__ __forceinline__ void prof_power(cpx<R> z, cpx<R> c, unsigned long lon
     clipped += clip;
     fx_accum(clip ? (R)kProfCap : p, l0, l1);
 }
+// The density record's LDS behind rx_carve's layout: G x G 32-bit bins (k_rx_dens and its launcher)
+template <typename CV>
+__host__ __device__ __forceinline__ constexpr uint32_t* dens_lds(CV& cv, int bins) {
+    return cv.template take<uint32_t>((size_t)bins * bins);
+}
+// One point into the density histogram (ofdm_hip.h, ofdm_rx_density: the index).  Per axis
+// t = (c - lo) * inv_w in double, one rounded subtraction and one rounded multiplication (no contraction:
+// a NumPy restatement reproduces it bit for bit); inside iff 0 <= t < G on both axes, which a NaN or an
+// infinity fails.  Inside: one LDS add without return; otherwise the lane's outside count.
+template <typename R>
+__device__ __forceinline__ void dens_bin(cpx<R> v, const RxDensTail& dt, uint32_t* hist, unsigned long long& outside) {
+#pragma clang fp contract(off)
+    const double g = (double)dt.bins;
+    const double tr = __dmul_rn(__dsub_rn((double)v.re, dt.lo), dt.inv_w);
+    const double ti = __dmul_rn(__dsub_rn((double)v.im, dt.lo), dt.inv_w);
+    if (tr >= 0.0 && tr < g && ti >= 0.0 && ti < g)
+        __hip_atomic_fetch_add(hist + (int)ti * dt.bins + (int)tr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else
+        ++outside;
+}
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
 __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB, LOGN, EQ, MV>())) void k_rx(
     RxArgs a) {
-    constexpr bool PROF = false, SWEEP = false, FRAMES = false;
+    constexpr bool PROF = false, SWEEP = false, FRAMES = false, DENS = false;
 #include "ofdm_rx_body.hpp"
 }
 
@@ -1456,7 +1476,7 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB,
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
 __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<R, FB, LOGN, EQ, MV, true>())) void k_rx_prof(
     RxArgs a) {
-    constexpr bool PROF = true, SWEEP = false, FRAMES = false;
+    constexpr bool PROF = true, SWEEP = false, FRAMES = false, DENS = false;
 #include "ofdm_rx_body.hpp"
 }
 
@@ -1471,10 +1491,34 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool WIDE = false>
 __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB, LOGN, EQ, MV>())) void k_rx_frames(
     RxArgs a, RxFramesTail ft) {
-    constexpr bool PROF = false, SWEEP = false, FRAMES = true, REF = false;
+    constexpr bool PROF = false, SWEEP = false, FRAMES = true, DENS = false, REF = false;
 #define OFDM_RX_BODY_FRAMES
 #include "ofdm_rx_body.hpp"
 #undef OFDM_RX_BODY_FRAMES
+}
+
+// The receiver that also bins every equalised point into the constellation-density record
+// (ofdm_rx_density, ofdm_hip.h: the definition): k_rx with DENS compiled in.  The G x G histogram is
+// 32-bit bins in LDS behind the receiver's own layout (dens_lds), zeroed once per workgroup and fed with
+// one ds_add_u32 (no return) per binned point; the points outside the square are a per-lane register
+// count.  At the end every non-empty bin of the workgroup issues one 64-bit integer atomic into the
+// record, and the workgroup's outside count one more.  Integers only: the record does not depend on the
+// grid, the batching or the rank count.  The throughput receivers fill the LDS at their own workgroup
+// shapes (about 156 of 160 KB at config b's), so the kernel takes the profile's one-wave-per-SIMD shape
+// (rx_block / rx_waves with PROF), which leaves the histogram its 64 KB.
+// The 32-bit bins cannot wrap: one symbol-loop iteration bins at most SPB * N points, and after
+// RxDensTail::flush = floor((2^32 - 1) / (SPB * N)) iterations the workgroup adds its bins to the record
+// and zeroes them, a barrier on either side (a flush every >= 2^18 iterations: nothing beside a run's
+// other work).  The density arguments are a second kernel parameter (RxDensTail) that only this kernel
+// has.  Instantiated for the generic kernel (and its WIDE form) and for the complex128 cyclic-prefix OFDM
+// throughput receivers of the bench shapes (ofdm_dens_inst.hpp).
+template <typename R, int LOGN, int EQ, int FB, bool MV, bool WIDE = false>
+__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<R, FB, LOGN, EQ, MV, true>())) void k_rx_dens(
+    RxArgs a, RxDensTail dt) {
+    constexpr bool PROF = false, SWEEP = false, FRAMES = false, DENS = true, REF = false;
+#define OFDM_RX_BODY_DENS
+#include "ofdm_rx_body.hpp"
+#undef OFDM_RX_BODY_DENS
 }
 
 // The one-pass SNR sweep receiver (ofdm_rx_sweep): every symbol is received once per SNR point of the
@@ -1488,7 +1532,7 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB,
 template <typename R, int LOGN, int EQ, int FB, bool MV>
 __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<R, FB, LOGN, EQ, MV, true>())) void k_rx_sweep(
     RxSweepArgs sa) {
-    constexpr bool PROF = false, SWEEP = true, FRAMES = false, REF = false, WIDE = false;
+    constexpr bool PROF = false, SWEEP = true, FRAMES = false, DENS = false, REF = false, WIDE = false;
     const RxArgs& a = sa.r;  // (a copy of its own that took each point's snr_lin in turn left the argument registers for memory)
 #define OFDM_RX_BODY_SWEEP
 #include "ofdm_rx_body.hpp"

@@ -1,0 +1,6 @@
+// complex64 instantiation of the density-record RX launcher (every k_rx_dens specialisation).
+#include "ofdm_dens_inst.hpp"
+
+namespace ofdm {
+OFDM_INSTANTIATE_RX_DENS(float)
+}  // namespace ofdm

@@ -214,6 +214,20 @@ struct RxFramesTail {
     uint32_t flen;
 };
 
+// ofdm_rx_density: the constellation-density record's arguments, a second kernel parameter behind RxArgs
+// (k_rx_dens only; every other receiver takes its arguments alone, as before).  The grid is what the
+// host made of it (ofdm_hip.h): the kernel sees lo and inv_w, never the extent.
+//   flush: symbol-loop iterations a workgroup makes before it must add its 32-bit LDS bins to the
+//   record and zero them -- the launcher's floor((2^32 - 1) / (points one iteration can bin)), so that no
+//   bin can wrap whatever the points do
+struct RxDensTail {
+    unsigned long long* hist;  // device uint64[bins * bins + 1] (row = imaginary bin; last: outside), accumulated
+    double lo, inv_w;
+    int bins;
+    int k_lo, k_hi;
+    uint32_t flush;
+};
+
 // ofdm_rx_sweep: the receiver's arguments (counters: device uint64[n_snr][2]; snr_lin, noise_on,
 // nr / ni, z_out, wide and profile of `r` unused: noise is always on) and the points' 10^(snr_db/10)
 struct RxSweepArgs {
@@ -303,6 +317,10 @@ hipError_t launch_rx_prof(int logn, const RxArgs& a, hipStream_t s);
 // the receiver with the per-frame error record (ofdm_frames_inst.hpp)
 template <typename R>
 hipError_t launch_rx_frames(int logn, const RxArgs& a, const RxFramesTail& f, hipStream_t s);
+
+// the receiver with the constellation-density record (ofdm_dens_inst.hpp)
+template <typename R>
+hipError_t launch_rx_dens(int logn, const RxArgs& a, const RxDensTail& d, hipStream_t s);
 
 // the one-pass SNR sweep receiver (ofdm_sweep_inst.hpp)
 template <typename R>

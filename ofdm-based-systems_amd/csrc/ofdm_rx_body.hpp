@@ -1,7 +1,9 @@
 // ofdm_rx_body.hpp -- the body of the fused receivers k_rx and k_rx_prof (ofdm_fused.hpp), included
 // into each kernel after its `constexpr bool PROF` (no include guard: included once per kernel).
 // In scope: the kernel's template parameters R, LOGN, EQ, FB, MV, REF, WIDE, its argument `RxArgs a`,
-// PROF, SWEEP and FRAMES.
+// PROF, SWEEP, FRAMES and DENS.
+// DENS (k_rx_dens only, which defines OFDM_RX_BODY_DENS around its include and has its second argument
+// `RxDensTail dt` in scope): every equalised point is also binned into the density histogram in LDS.
 // FRAMES (k_rx_frames only, which defines OFDM_RX_BODY_FRAMES around its include and has its second
 // argument `RxFramesTail ft` in scope): each symbol's counts are also added to its frame's pair.
 // SWEEP (k_rx_sweep only, which defines OFDM_RX_BODY_SWEEP around its include and has its argument
@@ -19,12 +21,19 @@
 #else
     static_assert(!FRAMES, "k_rx_frames defines OFDM_RX_BODY_FRAMES around its include");
 #endif
+#ifdef OFDM_RX_BODY_DENS
+    static_assert(DENS && !REF && !PROF && !SWEEP && !FRAMES &&
+                      (FB == 0 || (sizeof(R) == 8 && (FB == 1 || !(FB & 1)) && (FB == 1 || !MV))),
+                  "the density record: the generic kernel, or a complex128 cyclic-prefix OFDM QAM throughput receiver");
+#else
+    static_assert(!DENS, "k_rx_dens defines OFDM_RX_BODY_DENS around its include");
+#endif
 #ifdef OFDM_RX_BODY_SWEEP
 #define OFDM_RX_SNR_LIN snr_lin_pt  // the SNR of the point being received
 #else
 #define OFDM_RX_SNR_LIN a.snr_lin
 #endif
-    constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV, PROF || SWEEP>();
+    constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV, PROF || SWEEP || DENS>();
     using G = Geo<LOGN, BLK>;
     using C = cpx<R>;
     constexpr int N = G::N, E = G::E, TPS = G::TPS;
@@ -63,7 +72,7 @@
     constexpr int n_sweep = 0;
 #endif
     constexpr bool HOLD = SWEEP && F64_FAST;
-    const RxLds<R> lds = rx_carve<R, LOGN, EQ, FB, MV, PROF || SWEEP>(cv, cm.words_per_sym, tts_all, n_wide, n_sweep);
+    const RxLds<R> lds = rx_carve<R, LOGN, EQ, FB, MV, PROF || SWEEP || DENS>(cv, cm.words_per_sym, tts_all, n_wide, n_sweep);
     C *tw = lds.tw, *tt = lds.tt, *eqt = lds.eqt;
     AxisInfo* axis = lds.axis;
     unsigned char* rowmem = lds.rowmem;
@@ -72,6 +81,24 @@
     unsigned long long* redc = lds.redc;
     using OP = typename RxLds<R>::OP;
     OP* ordt = lds.ordt;
+#ifdef OFDM_RX_BODY_DENS
+    // DENS: the workgroup's histogram behind the receiver's layout, zeroed before the first barrier
+    uint32_t* const dhist = dens_lds(cv, dt.bins);
+    const int dcells = dt.bins * dt.bins;
+    for (int i = threadIdx.x; i < dcells; i += BLK) dhist[i] = 0;
+    unsigned long long dout = 0;  // the lane's points outside the square
+    uint32_t dleft = dt.flush;    // iterations until the bins must be flushed (RxDensTail)
+    // the workgroup's bins into the record: one 64-bit integer atomic per non-empty bin (between barriers)
+    auto dens_flush = [&](bool zero) {
+        for (int i = threadIdx.x; i < dcells; i += BLK) {
+            const uint32_t c = dhist[i];
+            if (c) {
+                atomicAdd(dt.hist + i, (unsigned long long)c);
+                if (zero) dhist[i] = 0;
+            }
+        }
+    };
+#endif
     constexpr bool EQ_LDS = eq_in_lds<R, FB, LOGN, EQ>();  // (rx_carve)
     // otherwise (throughput kernels at N = 4096, and the complex64 generic kernel) the lane's
     // coefficients are loaded before the FFT each symbol (L2-resident), so their latency hides
@@ -508,6 +535,15 @@
                         d &= vm;
                     }
                     bes += __popc(d);
+#ifdef OFDM_RX_BODY_DENS
+                    // DENS: the point k_rx_prof forms for its error vector (an order-0 subcarrier has none)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int k = t + (4 * q + j) * TPS;
+                        if ((int)((oc >> (8 * j)) & 0xFFu) / (int)sizeof(OP) == kUnusedOrder) continue;
+                        if (k >= dt.k_lo && k < dt.k_hi) dens_bin<R>(cscale(z[j], sc[j] * scale), dt, dhist, dout);
+                    }
+#endif
                     if constexpr (PROF) {
                         // per element: the masked bit count from its byte of d; the error vector from
                         // z times its MMSE scale and the 1/sqrt(N) the slicer folds in, against the
@@ -557,6 +593,15 @@
                     }
                     bes += __popc(d);
                     ses += PermSlicer<FB>::nonzero_bytes(d);
+#ifdef OFDM_RX_BODY_DENS
+                    // DENS: the point k_rx_prof forms for its error vector
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int k = t + (4 * q + j) * TPS;
+                        if (k >= dt.k_lo && k < dt.k_hi)
+                            dens_bin<R>(cscale(z[j], fold ? sc[j] * scale : scale), dt, dhist, dout);
+                    }
+#endif
                     if constexpr (PROF) {
                         // per element: the counts from its byte of d; the error vector from z times
                         // its MMSE scale (folded into the slicer) and the slicer's 1/sqrt(N), against
@@ -605,6 +650,10 @@
                         else
                             ridx = nn ? nn_decide<R>(v, cm, 0, cm.lut_len) : slicer(v);
                     }
+#ifdef OFDM_RX_BODY_DENS
+                    // DENS: the value the tap stores (an adaptive plan's order-0 subcarrier left above)
+                    if (k >= dt.k_lo && k < dt.k_hi) dens_bin<R>(v, dt, dhist, dout);
+#endif
                     const uint32_t tidx = tb.generic(i, b, off);
                     uint32_t d = ridx ^ tidx;
                     ses += d != 0u;
@@ -671,6 +720,16 @@
             be = se = 0;
         }
 #endif
+#ifdef OFDM_RX_BODY_DENS
+        // DENS: before a 32-bit bin could wrap (k_rx_dens), the bins go to the record and start again.
+        // The iteration count is the workgroup's, so every thread takes the branch together.
+        if (--dleft == 0) {
+            __syncthreads();
+            dens_flush(true);
+            __syncthreads();
+            dleft = dt.flush;
+        }
+#endif
         sym_sync<TPS>();  // W and the FFT row are rewritten by the next symbol
 #ifdef OFDM_RX_BODY_SWEEP
         }  // (the point loop: the next point's FFT rewrites the row too)
@@ -682,6 +741,13 @@
         if (be) atomicAdd((unsigned long long*)&a.counters[0], be);
         if (se) atomicAdd((unsigned long long*)&a.counters[1], se);
     }
+#ifdef OFDM_RX_BODY_DENS
+    // DENS: the workgroup's bins and its outside count into the record
+    __syncthreads();
+    dens_flush(false);
+    dout = block_sum<unsigned long long, BLK>(dout, redc);
+    if (threadIdx.x == 0 && dout) atomicAdd(dt.hist + dcells, dout);
+#endif
 #ifdef OFDM_RX_BODY_SWEEP
     // (be and se are zero here, and block_sum's barriers stand between the points' LDS sums and this
     // read)  counters[n_snr][2]: one integer atomic pair per point and workgroup

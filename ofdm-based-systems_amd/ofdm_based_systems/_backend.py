@@ -49,6 +49,8 @@ PROFILE_ROWS = 5
 # frames one run's per-frame record holds at most (LinkEngine.run(frame_symbols=...)): 2^24 frames of
 # two int64, 256 MiB
 MAX_FRAMES = 1 << 24
+# bins per axis of ofdm_rx_density's grid at most (OFDM_MAX_DENSITY_BINS)
+MAX_DENSITY_BINS = 128
 EQ_NONE, EQ_ZF, EQ_MMSE = 0, 1, 2
 PREFIX_CYCLIC, PREFIX_ZERO = 0, 1
 MOD_OFDM, MOD_SC = 0, 1
@@ -126,6 +128,9 @@ SIGNATURES = {
     # (ofdm_rx's arguments, frame_len, n_frames, frames; ofdm_rx_frames joined ABI 6 as an added entry point)
     "ofdm_rx_frames": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _I64, _F64, _I32, _VP, _I64, _I64,
                                       _I64, _VP, _VP, _I64, _I64, _I64, _VP]),
+    # (ofdm_rx's arguments, lo, inv_w, bins, k_lo, k_hi, hist; ofdm_rx_density joined ABI 6 as an added entry point)
+    "ofdm_rx_density": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _I64, _F64, _I32, _VP, _I64, _I64,
+                                       _I64, _VP, _VP, _I64, _F64, _F64, _I32, _I32, _I32, _VP]),
     # (snr_db: a host array of doubles, copied at the call)
     "ofdm_rx_sweep": (ctypes.c_int, [_VP, _VP, _VP, _U64, _VP, _I64, _c_f64p, _I32, _I64, _I64, _I64, _VP]),
     # (plan, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid_bits, counters)

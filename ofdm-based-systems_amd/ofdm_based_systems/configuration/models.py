@@ -81,6 +81,12 @@ class SimulationSettings(BaseSettings):
     frame_symbols: Optional[int] = Field(None, ge=1, description="OFDM symbols per frame: also report the frame "
                                          "error rate, the BER's standard error and the bit errors per frame "
                                          "(None: no frame record)")
+    constellation_density: Optional[int] = Field(None, ge=1, le=128, description="bins per axis: also report the "
+                                                 "density of the received points in the I/Q plane over the "
+                                                 "whole run (None: no density record)")
+    constellation_density_extent: Optional[float] = Field(None, gt=0, description="half-width L of the density's "
+                                                          "square [-L, L)^2 (None: 1.5 times the constellation's "
+                                                          "largest coordinate)")
 
     def __str__(self) -> str:
         lines = [

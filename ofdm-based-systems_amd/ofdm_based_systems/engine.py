@@ -42,6 +42,10 @@ above the nominal sample power (ofdm_tx_clip: a soft limiter directly after the 
 and the channel); every run of the engine then transmits the limited stream, its statistics describe it,
 and LinkStats carries the count of limited samples (integers, all-reduced behind the error counters).
 
+Constellation density: ``run(..., density=G)`` also bins every equalised point of the run into a G x G
+grid over a square of the I/Q plane (ofdm_rx_density: 32-bit bins in LDS per workgroup, integer atomics
+into a uint64 record behind the counters); :class:`ConstellationDensity` carries it.
+
 PAPR distribution: :meth:`LinkEngine.papr` bins the per-symbol PAPR of the stream ``run`` transmits
 (ofdm_papr: the transmitter's map and IFFT, no channel, no receiver) into an integer histogram on the
 device; :class:`PaprStats` carries it and its CCDF.
@@ -162,6 +166,54 @@ def frame_count(n_sym: int, frame_symbols) -> int:
 
 
 @dataclass
+class ConstellationDensity:
+    """Where the received points of a whole run fall in the I/Q plane (``ofdm_rx_density``,
+    include/ofdm_hip.h): every equalised point of the subcarriers in ``subcarriers`` binned into a G x G
+    grid over the square [-extent, extent)^2.  Accumulated on the device in integers: identical for any
+    batching and rank count."""
+    counts: np.ndarray     # int64 [G][G]: row = imaginary bin, column = real bin
+    outside: int           # points outside the square (NaN and infinities among them)
+    extent: float          # L
+    n_points: int          # counts.sum() + outside
+    subcarriers: tuple     # (k_lo, k_hi): the subcarriers binned, [k_lo, k_hi)
+
+    @property
+    def bins(self) -> int:
+        return int(self.counts.shape[0])
+
+    @property
+    def edges(self) -> np.ndarray:
+        """float64 [G + 1]: the bin edges of either axis, -L + 2 L j / G (for plotting; the device's
+        index is floor((c + L) * (G / (2 L))), see :func:`density_grid`)."""
+        G = self.bins
+        return -self.extent + (2.0 * self.extent / G) * np.arange(G + 1, dtype=np.float64)
+
+    def to_image(self, scale: int = 4):
+        """A PIL heat map ("L") of log(1 + counts), the imaginary axis pointing up, every bin
+        ``scale`` x ``scale`` pixels."""
+        from PIL import Image
+
+        lg = np.log1p(self.counts.astype(np.float64))
+        top = float(lg.max())
+        px = np.zeros(lg.shape, np.uint8) if top == 0.0 else np.round(255.0 * lg / top).astype(np.uint8)
+        img = Image.fromarray(px[::-1].copy())  # (uint8, two axes: mode "L")
+        return img.resize((self.bins * int(scale),) * 2, Image.NEAREST) if scale != 1 else img
+
+
+def density_grid(bins, extent) -> tuple:
+    """(lo, inv_w) of ofdm_rx_density's grid from G bins per axis over [-L, L): lo = -L and
+    inv_w = G / (2 L), formed here in double (the library never sees L).  ValueError for a G outside
+    [1, B.MAX_DENSITY_BINS] or an L that is not finite and positive."""
+    if isinstance(bins, bool) or int(bins) != bins or not 1 <= int(bins) <= B.MAX_DENSITY_BINS:
+        raise ValueError(f"density = {bins!r} is not a number of bins per axis in [1, {B.MAX_DENSITY_BINS}] "
+                         "(more than 128 bins per axis are not built)")
+    L = float(extent)
+    if not (math.isfinite(L) and L > 0.0):
+        raise ValueError(f"density_extent = {extent!r} is not a finite positive extent")
+    return -L, int(bins) / (2.0 * L)
+
+
+@dataclass
 class LinkStats:
     bit_errors: int
     symbol_errors: int
@@ -179,6 +231,7 @@ class LinkStats:
     clipped_samples: Optional[int] = None  # samples whose |x|^2 exceeded the threshold
     clip_samples: Optional[int] = None     # samples examined: N per OFDM symbol
     frames: Optional[FrameStats] = None    # run(..., frame_symbols=F)
+    density: Optional[ConstellationDensity] = None  # run(..., density=G)
 
 
 def default_papr_edges_db() -> np.ndarray:
@@ -360,6 +413,8 @@ class LinkEngine:
         the channel) at ``clip_db`` dB above the nominal mean power of a time sample
         (:func:`nominal_sample_power`); None: a linear transmitter."""
         self._nominal = (n_fft, list(luts), sc_lut)
+        # max over the LUT pool of max(|re|, |im|): the default extent of a density record is 1.5 of it
+        self.lut_reach = max(float(max(np.max(np.abs(np.real(l))), np.max(np.abs(np.imag(l))))) for l in luts)
         if clip_db is not None:
             self.clip_db, self.clip_a2 = float(clip_db), clip_threshold(clip_db, self.nominal_power)
             if max(len(l) for l in luts) > 256:
@@ -424,14 +479,22 @@ class LinkEngine:
             B.check(self._lib.ofdm_tx_clip(*args, float(self.clip_a2), B.ptr(clip_counters)))
 
     def rx(self, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits_d, sym0, n_sym,
-           n_valid, counters, z_out=None, z_keep=0, profile=None, frames=None, frame_symbols=None):
+           n_valid, counters, z_out=None, z_keep=0, profile=None, frames=None, frame_symbols=None,
+           density=None, density_params=None, density_subcarriers=None):
         """ofdm_rx, or with a profile record (device int64 [5][N]) ofdm_rx_profile, or with a frame
         record (``frames``: device int64 [n_frames][2] of the whole run, ``frame_symbols`` OFDM symbols
-        per frame) ofdm_rx_frames."""
+        per frame) ofdm_rx_frames, or with a density record (``density``: device int64 [G * G + 1],
+        ``density_params``: (lo, inv_w, G), ``density_subcarriers``: (k_lo, k_hi)) ofdm_rx_density."""
         args = (self.plan.handle, stream, B.ptr(y), B.ptr(nr), B.ptr(ni), int(seed), B.ptr(stats),
                 int(total_samples), float(snr_db), int(noise_on), B.ptr(bits_d), int(sym0), int(n_sym),
                 int(n_valid), B.ptr(counters), B.ptr(z_out), int(z_keep))
-        if frames is not None:
+        if density is not None:
+            if profile is not None or frames is not None:
+                raise ValueError("rx: a density record together with a profile or a frame record has no kernel")
+            lo, inv_w, G = density_params
+            B.check(self._lib.ofdm_rx_density(*args, float(lo), float(inv_w), int(G), int(density_subcarriers[0]),
+                                              int(density_subcarriers[1]), B.ptr(density)))
+        elif frames is not None:
             if profile is not None:
                 raise ValueError("rx: a profile and a frame record together have no kernel (PROF x FRAMES is not built)")
             B.check(self._lib.ofdm_rx_frames(*args, int(frame_symbols), int(frames.shape[0]), B.ptr(frames)))
@@ -542,15 +605,15 @@ class LinkEngine:
 
     def _route_fused(self, fused: Optional[bool], *, philox: bool, tap: bool, profile: bool, whole: bool) -> bool:
         """The route of a run: ``fused`` None takes the fused one when the plan has a fused form, the
-        streams are Philox, there is no received-symbol tap, no profile (a frame record counts as one:
-        k_link has neither) and every bit is compared; False forces the two-kernel path; True raises
+        streams are Philox, there is no received-symbol tap, no profile (a frame or density record counts
+        as one: k_link has none of them) and every bit is compared; False forces the two-kernel path; True raises
         where no fused form exists."""
         clip = self.clip_a2 is not None  # (asked first: a clipped engine never probes the library)
         can = not clip and self.has_fused and philox and not tap and not profile and whole
         if fused and not can:
             raise ValueError("no fused form for this run: ofdm_link takes a complex128 N = 1024 fixed 64-QAM "
                              "cyclic-prefix OFDM plan over a flat channel without equaliser, Philox streams, "
-                             "no received-symbol tap, no profile or frame record and every bit compared, and no clip level "
+                             "no received-symbol tap, no profile, frame record or density record and every bit compared, and no clip level "
                              "(clip_db: the limiter is not built into k_link)")
         return can if fused is None else bool(fused)
 
@@ -668,7 +731,9 @@ class LinkEngine:
                   group=None, y_budget: int = DEFAULT_Y_BUDGET, batch: Optional[int] = None,
                   n_valid_bits: Optional[int] = None, events: Optional[list] = None,
                   profile: bool = False, fused: Optional[bool] = None,
-                  frame_symbols: Optional[int] = None) -> "PendingLink":
+                  frame_symbols: Optional[int] = None, density: Optional[int] = None,
+                  density_extent: Optional[float] = None,
+                  density_subcarriers: Optional[tuple] = None) -> "PendingLink":
         """Enqueue global OFDM symbols [0, n_sym) (this rank's shard when ``group`` is set) on
         the current stream without waiting for them; :meth:`PendingLink.result` reads the
         counts back.  Back-to-back calls therefore keep the GPU busy while the host prepares
@@ -679,7 +744,7 @@ class LinkEngine:
                   for Philox noise
         events  : if a list, (kernel, n_symbols, start, end) HIP events are appended around
                   every ofdm_tx / ofdm_rx launch (recorded on the launch stream); with frame_symbols the
-                  receiver's are named "ofdm_rx_frames"
+                  receiver's are named "ofdm_rx_frames", with density "ofdm_rx_density"
         profile : accumulate the per-subcarrier record of the whole run (LinkStats.profile): bit and
                   symbol errors, error-vector power and clipped samples per subcarrier, summed on the
                   device in integers by every batch and, with a group, over the ranks -- exact, so
@@ -697,6 +762,19 @@ class LinkEngine:
                   keep_symbols = 0 run their throughput receiver with the record compiled in, every
                   other run the generic receiver.  At most B.MAX_FRAMES frames; not together with
                   ``profile``; the fused route has no record (None takes the two-kernel path).
+        density : G: accumulate the constellation density of the whole run (LinkStats.density,
+                  :class:`ConstellationDensity`): every equalised point -- the value the tap stores --
+                  binned into a G x G grid (G <= B.MAX_DENSITY_BINS) over the square [-L, L)^2, int64
+                  [G * G + 1] behind the counters (the last word counts the points outside).
+                  ``density_extent``: L (default 1.5 times the largest |re| or |im| of the plan's LUT
+                  pool); ``density_subcarriers``: (k_lo, k_hi), only subcarriers k_lo <= k < k_hi are
+                  binned (default the whole symbol).  ofdm_rx_density: the complex128 bench shapes with
+                  Philox streams and keep_symbols = 0 run their throughput receiver with the record
+                  compiled in, every other run the generic receiver -- a run with a tap on all its
+                  batches (the later ones are handed the tap buffer with z_keep = 0), so the record of
+                  any run is the same for every batching and rank count, exactly.  Not together with
+                  ``profile`` or ``frame_symbols``; the fused route has no record (None takes the
+                  two-kernel path).
         fused   : the route.  None: the fused one -- a power pass, then one ofdm_link launch that
                   transmits and receives every symbol of the shard in registers: no y buffer, no
                   batching -- when the plan has a fused form (has_fused), the streams are Philox
@@ -710,10 +788,28 @@ class LinkEngine:
                 raise ValueError("profile=True together with frame_symbols: the receiver with both records "
                                  "(PROF x FRAMES) is not built; run twice")
             n_frames = frame_count(n_sym, frame_symbols)
+        n_dens, dgrid, drange = 0, None, None
+        if density is not None:
+            if profile:
+                raise ValueError("profile=True together with density: the receiver with both records "
+                                 "(PROF x DENS) is not built; run twice")
+            if frame_symbols is not None:
+                raise ValueError("frame_symbols together with density: the receiver with both records "
+                                 "(FRAMES x DENS) is not built; run twice")
+            L = 1.5 * self.lut_reach if density_extent is None else float(density_extent)
+            dgrid = density_grid(density, L) + (int(density),)
+            drange = (0, self.n_fft) if density_subcarriers is None else tuple(int(k) for k in density_subcarriers)
+            if len(drange) != 2 or not 0 <= drange[0] < drange[1] <= self.n_fft:
+                raise ValueError(f"density_subcarriers = {density_subcarriers!r} is not a range "
+                                 f"0 <= k_lo < k_hi <= {self.n_fft}")
+            n_dens = int(density) ** 2 + 1
+        elif density_extent is not None or density_subcarriers is not None:
+            raise ValueError("density_extent / density_subcarriers without density")
         r = self._share(n_sym, group, n_valid_bits)
         dev, N = r.dev, self.n_fft
         use_link = self._route_fused(fused, philox=bits is None and normals is None, tap=keep_symbols > 0,
-                                     profile=profile or n_frames > 0, whole=r.n_valid >= n_sym * self.bps)
+                                     profile=profile or n_frames > 0 or n_dens > 0,
+                                     whole=r.n_valid >= n_sym * self.bps)
 
         bits_d = None
         if bits is not None:
@@ -727,11 +823,12 @@ class LinkEngine:
             ni_d = self.upload(np.asarray(normals[1], np.float64))
 
         stats = new_stats(dev)
-        # the counters, and behind them the clip record and the profile or frame record: one buffer, one
-        # all-reduce (every rank adds its own symbols' counts into the whole run's frame record)
+        # the counters, and behind them the clip record and the profile, frame or density record: one
+        # buffer, one all-reduce (every rank adds its own symbols' counts into the whole run's frame or
+        # density record)
         nclip = 0 if self.clip_a2 is None else 2
-        acc = torch.zeros(2 + nclip + (B.PROFILE_ROWS * N if profile else 0) + 2 * n_frames, dtype=torch.int64,
-                          device=dev)
+        acc = torch.zeros(2 + nclip + (B.PROFILE_ROWS * N if profile else 0) + 2 * n_frames + n_dens,
+                          dtype=torch.int64, device=dev)
         counters = acc[:2]
         clip = acc[2:4] if nclip else None
         prof = acc[2 + nclip:].view(B.PROFILE_ROWS, N) if profile else None
@@ -739,14 +836,21 @@ class LinkEngine:
         frec = acc[2 + nclip:].view(n_frames, 2) if n_frames else None
         if n_frames:  # (and without a frame record)
             pkw = {"frames": frec, "frame_symbols": int(frame_symbols)}
+        drec = acc[2 + nclip:] if n_dens else None
+        if n_dens:  # (and without a density record)
+            pkw = {"density": drec, "density_params": dgrid, "density_subcarriers": drange}
         keep = min(keep_symbols, r.mine)
         z_out = torch.empty((keep, N), dtype=self.cdtype, device=dev) if keep else None
+        rx_name = "ofdm_rx_density" if n_dens else "ofdm_rx_frames" if n_frames else "ofdm_rx"
 
         def receive(y, sym0, n, resident):
             zk = keep if sym0 == r.lo else 0  # the tap: the shard's first symbols, so its first batch
-            self._timed(events if resident else None, "ofdm_rx_frames" if n_frames else "ofdm_rx", n, lambda: self.rx(
+            # (a density record: the later batches of a run with a tap keep the tap buffer, z_keep = 0, so
+            # that every batch takes the generic receiver -- one form per run, ofdm_rx_density)
+            zo = z_out if zk or n_dens else None
+            self._timed(events if resident else None, rx_name, n, lambda: self.rx(
                 r.stream, y, nr_d, ni_d, seed, stats, r.samples, snr_db, noise_on, bits_d, sym0, n, r.n_valid,
-                counters, z_out if zk else None, zk, **pkw))
+                counters, zo, zk, **pkw))
 
         def link():
             self._timed(events, "ofdm_link", r.mine, lambda: self.link(
@@ -756,7 +860,8 @@ class LinkEngine:
                                     batch=batch, events=events, link=link if use_link else None, clip=clip)
         return PendingLink(n_sym, r.samples, stats, counters, z_out, done, work, prof,
                            self.bits_per_subcarrier if profile else None, clip=clip, clip_db=self.clip_db,
-                           frames=frec, frame_info=(int(frame_symbols), self.bps, r.n_valid) if n_frames else None)
+                           frames=frec, frame_info=(int(frame_symbols), self.bps, r.n_valid) if n_frames else None,
+                           density=drec, density_info=(dgrid[2], -dgrid[0], drange) if n_dens else None)
 
     # ------------------------------------------------------------------ one-pass SNR sweep
     def run_sweep(self, n_sym: int, snr_dbs, **kw) -> list:
@@ -767,7 +872,7 @@ class LinkEngine:
     def run_sweep_async(self, n_sym: int, snr_dbs, *, seed: int = 0, group=None,
                         y_budget: int = DEFAULT_Y_BUDGET, batch: Optional[int] = None,
                         n_valid_bits: Optional[int] = None, events: Optional[list] = None,
-                        frame_symbols: Optional[int] = None) -> "PendingSweep":
+                        frame_symbols: Optional[int] = None, density: Optional[int] = None) -> "PendingSweep":
         """Throughput-mode (Philox) runs of global OFDM symbols [0, n_sym) at every SNR of
         ``snr_dbs`` with one seed, from one transmit: point k is ``run(n_sym, snr_dbs[k], seed=seed)``
         -- the same bits, noise words, sigma and per-sample arithmetic, so in complex128 the same
@@ -780,8 +885,11 @@ class LinkEngine:
         counts do not depend on the batching, the rank count, the order of the list or how it is split.
 
         Not taken: caller bits or normals, orders above 256, a profile, a frame record
-        (``frame_symbols``: ValueError), a received-symbol tap, and a plan per point (adaptive loading
-        re-derived per SNR)."""
+        (``frame_symbols``: ValueError), a density record (``density``: ValueError), a received-symbol
+        tap, and a plan per point (adaptive loading re-derived per SNR)."""
+        if density is not None:
+            raise ValueError("run_sweep with density: the sweep receiver keeps no density record "
+                             "(the density inside k_rx_sweep is not built); use run per point")
         if frame_symbols is not None:
             raise ValueError("run_sweep with frame_symbols: the sweep receiver keeps no frame record "
                              "(frames inside k_rx_sweep are not built); use run per point")
@@ -822,7 +930,8 @@ class LinkEngine:
 
     def run_pipelined(self, n_sym: int, snr_db, seeds, *, group=None,
                       events: Optional[list] = None, y_budget: int = DEFAULT_Y_BUDGET, lanes: int = 1,
-                      fused: Optional[bool] = None, frame_symbols: Optional[int] = None) -> list:
+                      fused: Optional[bool] = None, frame_symbols: Optional[int] = None,
+                      density: Optional[int] = None) -> list:
         """Independent throughput-mode runs (one per seed) of global OFDM symbols [0, n_sym),
         software-pipelined across runs: run k+1's TX is enqueued before run k's RX, so with
         several ranks the statistics exchange of run k (the one collective on a run's
@@ -848,6 +957,9 @@ class LinkEngine:
                              "record; use run_async or run_sweep")
         if frame_symbols is not None:
             raise ValueError("run_pipelined with frame_symbols: the pipelined schedule carries no frame record; "
+                             "use run_async")
+        if density is not None:
+            raise ValueError("run_pipelined with density: the pipelined schedule carries no density record; "
                              "use run_async")
         seeds = list(seeds)
         snrs = list(snr_db) if isinstance(snr_db, (list, tuple, np.ndarray)) else [snr_db] * len(seeds)
@@ -945,11 +1057,14 @@ class PendingLink(_Pending):
     """Device-side results of one :meth:`LinkEngine.run_async` call."""
 
     def __init__(self, n_sym, samples, stats, counters, z_out, done=None, work=None, profile=None,
-                 bits_per_subcarrier=None, clip=None, clip_db=None, frames=None, frame_info=None):
+                 bits_per_subcarrier=None, clip=None, clip_db=None, frames=None, frame_info=None,
+                 density=None, density_info=None):
         self.n_sym, self.samples = n_sym, samples
         self.clip, self.clip_db = clip, clip_db
         # the run's frame record (device int64 [n_frames][2]) and (F, bits per OFDM symbol, bits compared)
         self.frames, self.frame_info = frames, frame_info
+        # the run's density record (device int64 [G * G + 1]) and (G, L, (k_lo, k_hi))
+        self.density, self.density_info = density, density_info
         self.stats, self.counters, self.z_out = stats, counters, z_out
         self.profile, self.bits_per_subcarrier = profile, bits_per_subcarrier
         self.done, self.work = done, work
@@ -972,9 +1087,15 @@ class PendingLink(_Pending):
             rec = self.frames.cpu().numpy().astype(np.int64)[:-(-self.n_sym // F)]  # (an empty run: no frame)
             fr = FrameStats(frame_symbols=F, n_symbols=self.n_sym, bits_per_symbol=bps, bit_errors=rec[:, 0].copy(),
                             symbol_errors=rec[:, 1].copy(), n_valid_bits=n_valid)
+        dens = None
+        if self.density is not None:
+            G, L, rng = self.density_info
+            rec = self.density.cpu().numpy().astype(np.int64)
+            dens = ConstellationDensity(counts=rec[:G * G].reshape(G, G).copy(), outside=int(rec[G * G]), extent=L,
+                                        n_points=int(rec.sum()), subcarriers=rng)
         return LinkStats(bit_errors=int(cnt[0]), symbol_errors=int(cnt[1]),
                          received=None if z is None else z.cpu().numpy().reshape(-1), profile=prof, frames=fr,
-                         **shared)
+                         density=dens, **shared)
 
 
 class PendingSweep(_Pending):

@@ -141,8 +141,19 @@ class Simulation:
         papr_edges_db=None,
         clip_db: Optional[float] = None,
         frame_symbols: Optional[int] = None,
+        constellation_density: Optional[int] = None,
+        constellation_density_extent: Optional[float] = None,
     ):
-        """frame_symbols: F: also return when the errors fall -- the bit errors of every frame of F
+        """constellation_density: G: also return where the received points of the whole run fall in the
+        I/Q plane -- every equalised point binned on the GPU into a G x G grid (G <= 128) over the square
+        [-L, L)^2, L = ``constellation_density_extent`` (default 1.5 times the constellation's largest
+        coordinate) (engine.ConstellationDensity, ``LinkEngine.run(density=G)``, ofdm_rx_density): the key
+        ``constellation_density`` = {``bins``, ``extent``, ``counts`` (nested lists, row = imaginary
+        bin), ``outside``, ``num_points``}.  Without it the result dict is unchanged; ``constellation_plot``
+        stays the scatter of the tapped symbols.  Needs the fused path (the built-in modulators, prefixes
+        and constellations); not combined with ``subcarrier_profile``, ``frame_symbols`` or ``run_sweep``.
+
+        frame_symbols: F: also return when the errors fall -- the bit errors of every frame of F
         consecutive OFDM symbols, accumulated on the GPU (engine.FrameStats, ``LinkEngine.run(
         frame_symbols=F)``, ofdm_rx_frames): the keys ``frame_symbols``, ``num_frames`` (full frames),
         ``frame_errors``, ``frame_error_rate``, ``ber_std_error`` (None with fewer than two full frames
@@ -208,6 +219,8 @@ class Simulation:
         self.papr_edges_db = papr_edges_db
         self.clip_db = clip_db
         self.frame_symbols = frame_symbols
+        self.constellation_density = constellation_density
+        self.constellation_density_extent = constellation_density_extent
 
     def _log(self, message: str) -> None:
         if self.verbose:
@@ -231,7 +244,9 @@ class Simulation:
             except Exception as e:  # noqa: BLE001
                 raise ValueError(f"Failed to load channel model from {path}: {e}")
         extra = {"rng_mode": s.rng_mode, "seed": s.seed, "precision": s.precision,
-                 "batch_symbols": s.batch_symbols, "clip_db": s.clip_db, "frame_symbols": s.frame_symbols}
+                 "batch_symbols": s.batch_symbols, "clip_db": s.clip_db, "frame_symbols": s.frame_symbols,
+                 "constellation_density": s.constellation_density,
+                 "constellation_density_extent": s.constellation_density_extent}
         return [
             cls(num_bits=s.num_bits, num_symbols=s.num_symbols, num_subcarriers=s.num_bands,
                 constellation_order=s.constellation_order, constellation_scheme=s.constellation_type,
@@ -330,6 +345,10 @@ class Simulation:
             raise ValueError("run_sweep with frame_symbols: the sweep receiver keeps no frame record; run the "
                              "simulations one by one")
 
+        if s0.constellation_density is not None:
+            raise ValueError("run_sweep with constellation_density: the sweep receiver keeps no density record; "
+                             "run the simulations one by one")
+
         swept: List[Any] = []  # the engine sweep's LinkStats, filled by the first simulation
 
         def link(k):
@@ -376,6 +395,22 @@ class Simulation:
         if self.subcarrier_profile:
             raise ValueError("frame_symbols with subcarrier_profile: the receiver with both records is not built")
 
+    def _check_density(self) -> None:
+        """What a density record is not combined with, refused before the run: user-supplied strategy
+        classes (the composed path keeps no record), the per-subcarrier profile, the frame record, a bad
+        grid."""
+        from ofdm_based_systems.engine import density_grid
+
+        L = self.constellation_density_extent
+        density_grid(self.constellation_density, 1.0 if L is None else L)  # (ValueError for a bad G or L)
+        if not self._builtin_strategies():
+            raise ValueError("constellation_density needs the built-in modulators, prefixes and constellations")
+        if self.subcarrier_profile:
+            raise ValueError("constellation_density with subcarrier_profile: the receiver with both records is "
+                             "not built")
+        if self.frame_symbols is not None:
+            raise ValueError("constellation_density with frame_symbols: the receiver with both records is not built")
+
     def _run(self, link=None) -> Dict[str, Any]:
         """run(); ``link`` (run_sweep): a callable (make_engine, n_sym, seed, valid_bits) -> LinkStats
         standing in for this simulation's own engine run."""
@@ -384,6 +419,8 @@ class Simulation:
             self._check_clip()  # (before anything is launched)
         if self.frame_symbols is not None:
             self._check_frames()
+        if self.constellation_density is not None:
+            self._check_density()
         sp = SerialToParallelConverter()
         noise_model = self.NOISE_SCHEME_MAPPERS.get(self.noise_scheme, AWGNoiseModel)()
         h_raw = np.asarray(DEFAULT_CHANNEL if self.channel_impulse_response is None
@@ -501,6 +538,8 @@ class Simulation:
             raise ValueError("subcarrier_profile needs the built-in modulators, prefixes and constellations")
         if not fused and self.frame_symbols is not None:  # (_check_frames saw the strategy classes)
             raise ValueError("frame_symbols needs the fused path (channel order and prefix within n_fft)")
+        if not fused and self.constellation_density is not None:  # (_check_density saw the strategy classes)
+            raise ValueError("constellation_density needs the fused path (channel order and prefix within n_fft)")
         if not fused and self.papr_ccdf:
             raise ValueError("papr_ccdf needs the built-in modulators, prefixes and constellations")
         if not fused and self.clip_db is not None:
@@ -532,7 +571,10 @@ class Simulation:
                              noise_on=noise_on, keep_symbols=self.received_symbols_keep,
                              group=self.process_group, batch=self.batch_symbols,
                              n_valid_bits=valid_bits, profile=self.subcarrier_profile,
-                             **({} if self.frame_symbols is None else {"frame_symbols": self.frame_symbols}))
+                             **({} if self.frame_symbols is None else {"frame_symbols": self.frame_symbols}),
+                             **({} if self.constellation_density is None else {
+                                 "density": self.constellation_density,
+                                 "density_extent": self.constellation_density_extent}))
             if self.papr_ccdf:
                 # the per-symbol PAPR distribution of the stream just transmitted: the same plan, seed
                 # and (reference mode) the run's own bits
@@ -577,6 +619,15 @@ class Simulation:
                 "ber_std_error": fr.ber_stderr,
                 "bit_errors_per_frame": fr.bit_errors.tolist(),
             })
+        if self.constellation_density is not None:
+            d = st.density
+            results["constellation_density"] = {
+                "bins": d.bins,
+                "extent": d.extent,
+                "counts": d.counts.tolist(),
+                "outside": d.outside,
+                "num_points": d.n_points,
+            }
         if self.clip_db is not None:
             results.update({
                 "clip_db": float(self.clip_db),
