@@ -39,6 +39,16 @@ extern "C" {
  * points' SNRs in their arguments); a longer list is split into several calls over the same y. */
 #define OFDM_MAX_SWEEP_POINTS 40
 
+/* The supported symbol range: every entry point that takes sym0 and n_sym (ofdm_tx, ofdm_tx_clip,
+ * ofdm_rx, ofdm_rx_profile, ofdm_rx_frames, ofdm_rx_density, ofdm_rx_sweep, the four ofdm_link* and
+ * ofdm_papr) returns OFDM_E_INVALID, before any launch, when sym0 + n_sym > OFDM_MAX_SYMBOLS.
+ * The host and the kernels form global bit positions s * bps + offset in int64_t (the n_valid_bits
+ * mask, the caller's bits and their byte count), s < sym0 + n_sym and bps the bits per OFDM symbol.
+ * The largest plan has 4096 subcarriers of 12 bits (4096-QAM): bps <= 49152 < 2^16, and an offset
+ * inside one symbol is below bps.  With s <= 2^46 every such value stays below 2^46 * 2^16 = 2^62,
+ * a factor of two inside int64_t, so no product, sum or rounding up to bytes can wrap. */
+#define OFDM_MAX_SYMBOLS ((int64_t)1 << 46)
+
 #define OFDM_OK 0
 #define OFDM_E_INVALID (-1)  /* bad argument / unsupported shape          */
 #define OFDM_E_HIP (-2)      /* HIP runtime error                          */

@@ -761,6 +761,15 @@ static int stream_bits_ok(ofdm_plan_t p, const uint8_t* bits, const char* who) {
                                     "; pass the tx bits (reference-stream mode)");
 }
 
+// The supported symbol range (OFDM_MAX_SYMBOLS, ofdm_hip.h): asked after sym0 >= 0 and n_sym >= 0 are
+// known, and formed as a difference, so that nothing wraps for any pair of int64_t values.
+static int symbols_ok(const char* who, int64_t sym0, int64_t n_sym) {
+    if (sym0 <= OFDM_MAX_SYMBOLS && n_sym <= OFDM_MAX_SYMBOLS - sym0) return OFDM_OK;
+    return fail(OFDM_E_INVALID, std::string(who) + ": symbols [" + std::to_string(sym0) + ", " + std::to_string(sym0) +
+                                    " + " + std::to_string(n_sym) + ") reach beyond OFDM_MAX_SYMBOLS = 2^46, the "
+                                    "supported symbol range");
+}
+
 static void fill_common(ofdm_plan_t p, TxRxCommon& c, const uint8_t* bits, uint64_t seed, int64_t sym0,
                         int64_t n_sym, int64_t total_syms_for_bits) {
     c.bits = bits;
@@ -814,6 +823,7 @@ static int tx_call(const char* who, ofdm_plan_t p, void* stream, const uint8_t* 
         return fail(OFDM_E_INVALID, std::string(who) + " needs a constellation and channel taps");
     if (p->L - 1 > p->n) return fail(OFDM_E_INVALID, "fused path needs channel order <= n_fft");
     if (n_sym < 0 || sym0 < 0 || !stats) return fail(OFDM_E_INVALID, std::string("bad argument to ") + who);
+    if (int rc = symbols_ok(who, sym0, n_sym)) return rc;
     if (clip) {
         if (!std::isfinite(clip->a2) || !(clip->a2 > 0.0))
             return fail(OFDM_E_INVALID, "ofdm_tx_clip: clip_a2 is not a finite positive threshold on |x|^2");
@@ -879,6 +889,7 @@ static int rx_args(const char* who, ofdm_plan_t p, const void* y, const double* 
     if (!p || !p->has_const) return fail(OFDM_E_INVALID, std::string(who) + " needs a constellation");
     if (p->eq != OFDM_EQ_NONE && !p->has_channel) return fail(OFDM_E_INVALID, "plan has no channel response");
     if (n_sym < 0 || sym0 < 0 || !counters) return fail(OFDM_E_INVALID, bad);
+    if (int rc = symbols_ok(who, sym0, n_sym)) return rc;
     if (int rc = own()) return rc;
     if (int rc = stream_bits_ok(p, bits, who)) return rc;
     if (n_sym == 0) return OFDM_OK;
@@ -1145,6 +1156,7 @@ int ofdm_papr(ofdm_plan_t p, void* stream, const uint8_t* bits, uint64_t seed, i
               const double* edges, int32_t n_edges, uint64_t* hist, double* sym_out, int64_t sym_keep) {
     if (!p || !p->has_const) return fail(OFDM_E_INVALID, "ofdm_papr needs a constellation");
     if (n_sym < 0 || sym0 < 0 || !hist) return fail(OFDM_E_INVALID, "bad argument to ofdm_papr");
+    if (int rc = symbols_ok("ofdm_papr", sym0, n_sym)) return rc;
     if (n_edges < 1 || n_edges > OFDM_MAX_PAPR_EDGES)
         return fail(OFDM_E_INVALID, "ofdm_papr takes 1 to " + std::to_string(OFDM_MAX_PAPR_EDGES) +
                                         " edges per call, got " + std::to_string(n_edges));

@@ -134,6 +134,7 @@ def lane_generators(seed: int, s: np.ndarray, N: int) -> LaneStream:
     """One lane block per (symbol, lane), lanes in row-major (s, t) order."""
     E, tps = geometry(N)
     s = np.asarray(s, dtype=np.int64)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF  # (a negative seed reaches the kernels as its two's complement)
     ss = np.repeat(s, tps).astype(np.uint64)
     t = np.tile(np.arange(tps, dtype=np.uint64), len(s))
     p = philox4x32_10(t, ss & MASK32, ss >> np.uint64(32), np.full_like(t, K_LANE),
@@ -229,14 +230,25 @@ class PhiloxLink:
     bracket: Optional[tuple] = None
     # the same for the per-point statistical deviation scale (run_philox(stat_sigma=...))
     stat_bracket: Optional[tuple] = None
+    z: Optional[np.ndarray] = None      # (S, N) equalised points, the values the decisions are made on
+    delta: Optional[np.ndarray] = None  # (S, N) z_error_bound on a GPU run's deviation from z (precision given)
 
 
 def run_philox(seed: int, S: int, N: int, M: int, h_raw: np.ndarray, cp: int, eq: str, snr_db: float,
                noise_on: bool = True, modulator: str = "OFDM", prefix: str = "CP",
                scheme: str = "QAM", orders=None, precision: Optional[str] = None, radius_fn=None,
                power_sum: Optional[float] = None, stat_sigma: Optional[float] = None,
-               stat_k: float = STAT_K) -> PhiloxLink:
-    """Global OFDM symbols [0, S) of a throughput-mode run, through the oracle arithmetic.
+               stat_k: float = STAT_K, sym0: int = 0, total_samples: Optional[int] = None) -> PhiloxLink:
+    """Global OFDM symbols [sym0, sym0 + S) of a throughput-mode run, through the oracle arithmetic.
+
+    sym0: the first global symbol (a Python int of any size below 2^63: the lane blocks take it in two
+    32-bit words).  With more than one channel tap and sym0 > 0 the first symbol carries the tail of
+    symbol sym0 - 1 through the channel, as a transmitter called at sym0 regenerates it: that symbol is
+    generated too, convolved, and its row dropped -- every returned field (the power sums and the peak,
+    idx, y, the counts and the brackets) covers [sym0, sym0 + S) only.  total_samples: the sample
+    count of the whole stream the noise power is a mean over (sigma^2 = power_sum / total_samples /
+    snr; default S (N + cp), this call's own): with the whole stream's power_sum and total_samples the
+    calls over the pieces of a stream see the whole stream's noise.
 
     modulator "OFDM" | "SC" (modulation/models.py:58-91), prefix "CP" | "ZP"
     (prefix/models.py:29-101), scheme "QAM" | "PSK".  With zero padding every lane's noise
@@ -245,8 +257,8 @@ def run_philox(seed: int, S: int, N: int, M: int, h_raw: np.ndarray, cp: int, eq
 
     orders: per-subcarrier QAM orders (CAPACITY_BASED bit loading, 0 = unused; M is then
     ignored).  As in the reference's decode (constellation/adaptive.py:259-263) a trailing
-    partial byte of the whole run's bit stream is not compared; symbol errors count every
-    used subcarrier.
+    partial byte of the whole run's bit stream -- the stream [0, sym0 + S) -- is not compared;
+    symbol errors count every used subcarrier.
 
     precision "f32" | "f64": also return the decision bracket of a GPU run in that arithmetic
     (PhiloxLink.bracket, see decision_bracket).
@@ -264,7 +276,11 @@ def run_philox(seed: int, S: int, N: int, M: int, h_raw: np.ndarray, cp: int, eq
     the worst case of the whole transform, c log2(N) u sqrt(N) rms).
     """
     E, tps = geometry(N)
-    gen = lane_generators(seed, np.arange(S), N)
+    sym0 = int(sym0)
+    gen = lane_generators(seed, sym0 + np.arange(S, dtype=np.int64), N)
+    # the predecessor's symbol, when its tail reaches into this call's first symbol
+    pre = 1 if (sym0 > 0 and len(np.atleast_1d(h_raw)) > 1) else 0
+    genp = lane_generators(seed, np.array([sym0 - 1], np.int64), N) if pre else None
     want_bound = precision is not None and noise_on
     prel = 2.0 ** -53 if precision == "f64" else 2.0 ** -24
     if orders is not None:
@@ -273,23 +289,24 @@ def run_philox(seed: int, S: int, N: int, M: int, h_raw: np.ndarray, cp: int, eq
         idx = tx_indices(gen, S, N, bk)
         make = O.psk_lut if scheme == "PSK" else O.qam_lut
         luts = {int(o): make(int(o)) for o in np.unique(orders) if o > 0}
-        X = np.zeros((S, N), np.complex128)
+        ia = np.concatenate([tx_indices(genp, 1, N, bk), idx]) if pre else idx
+        X = np.zeros((S + pre, N), np.complex128)
         for o, lt in luts.items():
             cols = orders == o
-            X[:, cols] = lt[idx[:, cols]]
+            X[:, cols] = lt[ia[:, cols]]
     else:
         b = int(np.log2(M))
         lut = O.qam_lut(M) if scheme == "QAM" else O.psk_lut(M)
         idx = tx_indices(gen, S, N, b)
-        X = lut[idx]
+        X = lut[np.concatenate([tx_indices(genp, 1, N, b), idx]) if pre else idx]
     s_t = np.fft.ifft(X, axis=1, norm="ortho") if modulator == "OFDM" else X
     if prefix == "ZP":
-        x = np.concatenate([s_t, np.zeros((S, cp), np.complex128)], axis=1)
+        x = np.concatenate([s_t, np.zeros((S + pre, cp), np.complex128)], axis=1)
     else:
         x = O.add_cp(s_t, cp)                          # (S, N+cp) incl. prefix
-    px = float(np.sum(np.abs(x) ** 2))
-    mx = float(np.max(np.abs(x) ** 2))
-    y = O.channel_conv(x.ravel(), np.asarray(h_raw, np.complex128)).reshape(S, N + cp)
+    px = float(np.sum(np.abs(x[pre:]) ** 2))
+    mx = float(np.max(np.abs(x[pre:]) ** 2))
+    y = O.channel_conv(x.ravel(), np.asarray(h_raw, np.complex128)).reshape(S + pre, N + cp)[pre:]
     py = float(np.sum(np.abs(y) ** 2))
     if prefix == "ZP":
         yk, tail = y[:, :N].copy(), y[:, N:].copy()
@@ -301,7 +318,7 @@ def run_philox(seed: int, S: int, N: int, M: int, h_raw: np.ndarray, cp: int, eq
     nbs = np.zeros((S, N))
     if noise_on:
         # sigma^2 = mean |y|^2 / snr (noise/models.py:13-18), as k_rx evaluates it in double
-        p = (py if power_sum is None else float(power_sum)) / (S * (N + cp))
+        p = (py if power_sum is None else float(power_sum)) / (S * (N + cp) if total_samples is None else int(total_samples))
         sigma = float(np.sqrt((p / 10 ** (snr_db / 10)) / 2.0))
         if want_bound:
             nz, nb = lane_noise(gen, S, N, sigma, with_bound=True, radius_fn=radius_fn, product_rel=prel)
@@ -328,7 +345,7 @@ def run_philox(seed: int, S: int, N: int, M: int, h_raw: np.ndarray, cp: int, eq
     Z = O.equalize(Y, H, eq, snr_db)
     if modulator == "SC":
         Z = np.fft.ifft(Z, axis=1, norm="ortho")
-    bracket = stat_bracket = None
+    bracket = stat_bracket = delta = None
     if precision is not None:
         delta = z_error_bound(precision, Y, H, eq, snr_db, nerr, modulator, N, np.sqrt(nerr2))
         dstat = None
@@ -339,9 +356,9 @@ def run_philox(seed: int, S: int, N: int, M: int, h_raw: np.ndarray, cp: int, eq
             dstat = z_stat_bound(precision, Y, H, eq, snr_db, sig, np.sqrt(np.mean(np.abs(yk) ** 2)),
                                  modulator, N, stat_k)
         if orders is not None:
-            bracket = adaptive_bracket(Z, idx, orders, bk, delta, scheme)
+            bracket = adaptive_bracket(Z, idx, orders, bk, delta, scheme, sym0)
             if dstat is not None:
-                stat_bracket = adaptive_bracket(Z, idx, orders, bk, dstat, scheme)
+                stat_bracket = adaptive_bracket(Z, idx, orders, bk, dstat, scheme, sym0)
         else:
             bracket = decision_bracket(Z, idx, lut, b, delta, scheme)
             if dstat is not None:
@@ -352,27 +369,28 @@ def run_philox(seed: int, S: int, N: int, M: int, h_raw: np.ndarray, cp: int, eq
             cols = np.flatnonzero(orders == o)
             ridx[:, cols] = O.nn_demap(Z[:, cols].ravel(), lt).reshape(S, len(cols))
         diff = (ridx ^ idx).astype(np.int64)
-        be, se = adaptive_counts(diff, bk, S)
-        return PhiloxLink(be, se, py, px, mx, idx, y if prefix == "ZP" else yk, bracket, stat_bracket)
+        be, se = adaptive_counts(diff, bk, S, sym0)
+        return PhiloxLink(be, se, py, px, mx, idx, y if prefix == "ZP" else yk, bracket, stat_bracket, Z, delta)
     ridx = O.nn_demap(Z.ravel(), lut).reshape(S, N)
     diff = (ridx ^ idx).astype(np.uint64)
     be = int(sum(int(np.count_nonzero((diff >> np.uint64(j)) & np.uint64(1))) for j in range(b)))
     se = int(np.count_nonzero(ridx != idx))
-    return PhiloxLink(be, se, py, px, mx, idx, y if prefix == "ZP" else yk, bracket, stat_bracket)
+    return PhiloxLink(be, se, py, px, mx, idx, y if prefix == "ZP" else yk, bracket, stat_bracket, Z, delta)
 
 
-def adaptive_counts(diff: np.ndarray, bk: np.ndarray, S: int):
-    """Bit / symbol errors of CAPACITY_BASED decisions (diff = rx ^ tx index per (s, k)): the
-    stream position of bit j (MSB first) of subcarrier k in symbol s is s*tot + off_k + j, and a
-    trailing partial byte of the run is not compared (constellation/adaptive.py:259-263)."""
+def adaptive_counts(diff: np.ndarray, bk: np.ndarray, S: int, sym0: int = 0):
+    """Bit / symbol errors of CAPACITY_BASED decisions (diff = rx ^ tx index per (s, k)) of global
+    symbols [sym0, sym0 + S): the stream position of bit j (MSB first) of subcarrier k in symbol s is
+    s*tot + off_k + j, and a trailing partial byte of the run [0, sym0 + S) is not compared
+    (constellation/adaptive.py:259-263).  (tot < 2^16 and s < 2^46: the positions fit int64.)"""
     tot = int(bk.sum())
-    valid = (S * tot // 8) * 8
+    valid = ((sym0 + S) * tot // 8) * 8
     off = np.concatenate([[0], np.cumsum(bk)[:-1]])
     be = 0
     for j in range(int(bk.max(initial=0))):
         has = bk > j
         bit = (diff >> np.maximum(bk - 1 - j, 0)[None, :]) & 1
-        pos = np.arange(S)[:, None] * tot + (off + j)[None, :]
+        pos = (sym0 + np.arange(S, dtype=np.int64))[:, None] * tot + (off + j)[None, :]
         be += int(np.count_nonzero(bit.astype(bool) & has[None, :] & (pos < valid)))
     se = int(np.count_nonzero(diff[:, bk > 0]))
     return be, se
@@ -536,7 +554,7 @@ def decision_bracket(Z: np.ndarray, idx: np.ndarray, lut: np.ndarray, b: int, de
 
 
 def adaptive_bracket(Z: np.ndarray, idx: np.ndarray, orders: np.ndarray, bk: np.ndarray,
-                     delta: np.ndarray, scheme: str = "QAM") -> tuple:
+                     delta: np.ndarray, scheme: str = "QAM", sym0: int = 0) -> tuple:
     """decision_bracket for CAPACITY_BASED loading: per order, the candidates of its subcarriers
     over that order's LUT (QAM or PSK); bit errors counted as adaptive_counts does (trailing
     partial byte excluded)."""
@@ -551,7 +569,7 @@ def adaptive_bracket(Z: np.ndarray, idx: np.ndarray, orders: np.ndarray, bk: np.
         cs = decision_candidates(Z[:, cols], make(int(o)), d[:, cols], scheme)
         for c, v in zip(cand, cs):
             c[:, cols] = v.reshape(S, len(cols))
-    be0, _ = adaptive_counts((cand[0] ^ idx).astype(np.int64), bk, S)
+    be0, _ = adaptive_counts((cand[0] ^ idx).astype(np.int64), bk, S, sym0)
     # the other candidates change an element's bit count by at most the spread of its popcounts
     diffs = np.stack([_popcount(c ^ idx) for c in cand])
     used = (bk > 0)[None, :]

@@ -89,12 +89,17 @@ class ClippedLink:
 
 def run_clipped(seed, S, N, M, h_raw, cp, eq, snr_db, a2, noise_on=True, modulator="OFDM", prefix="CP",
                 scheme="QAM", orders=None, luts=None, sc_lut=None, precision=None, radius_fn=None, power_sum=None,
-                stat_sigma=None, stat_k=P.STAT_K, clip=True) -> ClippedLink:
+                stat_sigma=None, stat_k=P.STAT_K, clip=True, sym0=0) -> ClippedLink:
     """philox_streams.run_philox with the limiter at threshold ``a2`` on |x|^2 (clip=False: without it, the
     same body).  Adaptive loading: either ``orders`` (per-subcarrier QAM / PSK orders, as run_philox) or the
-    plan's own ``luts`` / ``sc_lut`` (papr_expect.adaptive_2048)."""
+    plan's own ``luts`` / ``sc_lut`` (papr_expect.adaptive_2048).  sym0: global symbols [sym0, sym0 + S), as
+    run_philox takes it: on a multipath channel the (limited) symbol sym0 - 1 is generated too and its row
+    dropped after the channel; every field covers [sym0, sym0 + S) only."""
     E, tps = P.geometry(N)
-    gen = P.lane_generators(seed, np.arange(S), N)
+    sym0 = int(sym0)
+    gen = P.lane_generators(seed, sym0 + np.arange(S, dtype=np.int64), N)
+    pre = 1 if (sym0 > 0 and len(np.atleast_1d(h_raw)) > 1) else 0
+    genp = P.lane_generators(seed, np.array([sym0 - 1], np.int64), N) if pre else None
     want_bound = precision is not None and noise_on
     prel = 2.0 ** -53 if precision == "f64" else 2.0 ** -24
     if orders is None and sc_lut is not None:
@@ -107,26 +112,28 @@ def run_clipped(seed, S, N, M, h_raw, cp, eq, snr_db, a2, noise_on=True, modulat
         idx = P.tx_indices(gen, S, N, bk)
         make = O.psk_lut if scheme == "PSK" else O.qam_lut
         tabs = {int(o): make(int(o)) for o in np.unique(orders) if o > 0}
-        X = np.zeros((S, N), np.complex128)
+        ia = np.concatenate([P.tx_indices(genp, 1, N, bk), idx]) if pre else idx
+        X = np.zeros((S + pre, N), np.complex128)
         for o, lt in tabs.items():
             cols = orders == o
-            X[:, cols] = lt[idx[:, cols]]
+            X[:, cols] = lt[ia[:, cols]]
     else:
         b = int(np.log2(M))
         lut = O.qam_lut(M) if scheme == "QAM" else O.psk_lut(M)
         idx = P.tx_indices(gen, S, N, b)
-        X = lut[idx]
+        X = lut[np.concatenate([P.tx_indices(genp, 1, N, b), idx]) if pre else idx]
     s_t = np.fft.ifft(X, axis=1, norm="ortho") if modulator == "OFDM" else X
     p_raw = s_t.real ** 2 + s_t.imag ** 2
     if clip:
         s_t, p_raw = limit(s_t, a2)
+    p_raw, X = p_raw[pre:], X[pre:]
     if prefix == "ZP":
-        x = np.concatenate([s_t, np.zeros((S, cp), np.complex128)], axis=1)
+        x = np.concatenate([s_t, np.zeros((S + pre, cp), np.complex128)], axis=1)
     else:
         x = O.add_cp(s_t, cp)
-    px = float(np.sum(np.abs(x) ** 2))
-    mx = float(np.max(np.abs(x) ** 2))
-    y = O.channel_conv(x.ravel(), np.asarray(h_raw, np.complex128)).reshape(S, N + cp)
+    px = float(np.sum(np.abs(x[pre:]) ** 2))
+    mx = float(np.max(np.abs(x[pre:]) ** 2))
+    y = O.channel_conv(x.ravel(), np.asarray(h_raw, np.complex128)).reshape(S + pre, N + cp)[pre:]
     py = float(np.sum(np.abs(y) ** 2))
     if prefix == "ZP":
         yk, tail = y[:, :N].copy(), y[:, N:].copy()
@@ -171,9 +178,9 @@ def run_clipped(seed, S, N, M, h_raw, cp, eq, snr_db, a2, noise_on=True, modulat
             dstat = P.z_stat_bound(precision, Y, H, eq, snr_db, sig, np.sqrt(np.mean(np.abs(yk) ** 2)),
                                    modulator, N, stat_k)
         if orders is not None:
-            bracket = P.adaptive_bracket(Z, idx, orders, bk, delta, scheme)
+            bracket = P.adaptive_bracket(Z, idx, orders, bk, delta, scheme, sym0)
             if dstat is not None:
-                stat_bracket = P.adaptive_bracket(Z, idx, orders, bk, dstat, scheme)
+                stat_bracket = P.adaptive_bracket(Z, idx, orders, bk, dstat, scheme, sym0)
         else:
             bracket = P.decision_bracket(Z, idx, lut, b, delta, scheme)
             if dstat is not None:
@@ -184,7 +191,7 @@ def run_clipped(seed, S, N, M, h_raw, cp, eq, snr_db, a2, noise_on=True, modulat
         for o, lt in tabs.items():
             cols = np.flatnonzero(orders == o)
             ridx[:, cols] = O.nn_demap(Z[:, cols].ravel(), lt).reshape(S, len(cols))
-        be, se = P.adaptive_counts((ridx ^ idx).astype(np.int64), bk, S)
+        be, se = P.adaptive_counts((ridx ^ idx).astype(np.int64), bk, S, sym0)
         act = orders > 0
         evm = float(np.mean(np.abs(Z[:, act] - X[:, act]) ** 2)) if act.any() else 0.0
     else:

@@ -102,11 +102,17 @@ def bracket(Z, delta, G, L, k_lo=0, k_hi=None, active=None):
     return decided, maybe
 
 
-def philox_points(seed, S, N, M, h_raw, cp, eq, snr_db, orders=None, radius_fn=None, power_sum=None):
+def philox_points(seed, S, N, M, h_raw, cp, eq, snr_db, orders=None, radius_fn=None, power_sum=None, sym0=0):
     """(Z, delta, idx) of a complex128 cyclic-prefix OFDM throughput-mode run: the equalised points of
-    philox_streams.run_philox (the same calls in the same order; run_philox returns the counts only),
+    philox_streams.run_philox (the same calls in the same order, written out for sym0 = 0),
     the per-point bound z_error_bound puts on a GPU run's deviation from them, and the transmitted
-    indices.  radius_fn / power_sum: the device's noise radii and the run's exact power (run_philox)."""
+    indices.  radius_fn / power_sum: the device's noise radii and the run's exact power (run_philox).
+    sym0 > 0: global symbols [sym0, sym0 + S), run_philox's own z, delta and idx at that sym0 (at sym0 = 0
+    they equal the ones written out here: tests/test_stream_range_cpu.py)."""
+    if sym0:
+        r = P.run_philox(seed, S, N, M, h_raw, cp, eq, snr_db, orders=orders, precision="f64", radius_fn=radius_fn,
+                         power_sum=power_sum, sym0=sym0)
+        return r.z, r.delta, r.idx
     gen = P.lane_generators(seed, np.arange(S), N)
     if orders is not None:
         orders = np.asarray(orders, np.int64)
