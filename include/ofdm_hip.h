@@ -158,7 +158,15 @@ int ofdm_map(ofdm_plan_t plan, void* stream, const uint8_t* bytes, int64_t n_byt
 /* QAMConstellationMapper.decode (constellation/models.py:251-295): nearest LUT point
    by brute-force |z - C_m| argmin (first index on ties, NNClassifier :19-27), bits
    packed MSB-first; fixed mode writes ceil(n*b/8) bytes (tail zero-padded), adaptive
-   mode floor(S*sum(b)/8) bytes (constellation/adaptive.py:257-265). */
+   mode floor(S*sum(b)/8) bytes (constellation/adaptive.py:257-265).
+   Zero components (the per-axis path of sides 32 and 64, ofdm_demap_count and the fused receivers,
+   which round a level coordinate where this searches): a real or imaginary part that is exactly
+   +-0 lies halfway between the two central levels of a square QAM, and 0+0j ties between its four
+   central points -- what an MMSE equaliser puts out on a subcarrier whose channel response is
+   exactly zero, in every OFDM symbol.  The decision there is the argmin's: the first index, which
+   for the reference's LUTs is the lower central level on I and the upper one on Q.  Every plan reads
+   the two levels off each LUT when it is created (the levels of LUT[argmin |C_m|]); they are not
+   left to how lev0 / step rounds. */
 int ofdm_demap(ofdm_plan_t plan, void* stream, const void* z, int64_t n, uint8_t* bytes);
 
 /* QAMConstellationMapper.decode (constellation/models.py:251-295) or
@@ -254,6 +262,13 @@ int ofdm_power(ofdm_plan_t plan, void* stream, const void* y, int64_t len, doubl
  *   (sample s*(N+cp)+m); NULL -> the throughput-mode lane streams, Box-Muller.
  *   z_out (optional): the equalised symbols of the first z_keep OFDM symbols of this
  *   call, (z_keep, N) complex -- the results' received_symbols (simulation/models.py:618).
+ *   Null bins: a plan whose channel response is exactly 0 on a subcarrier (taps such as [1, -1])
+ *   is a legal plan.  Under MMSE the equalised symbol there is exactly 0 in every OFDM symbol and
+ *   decides the first of the four central points, as the reference's argmin does (see ofdm_demap:
+ *   the zero-component rule); such a plan's receivers -- ofdm_rx and every ofdm_rx_* form -- run
+ *   the generic kernel, whose slicer applies the rule, whatever the shape and the streams.  Under
+ *   ZF the reference divides by 1e-10 there: the symbol is the noise times 1e10, decided by its
+ *   signs (the level coordinate is clamped before it is converted to an integer).
  */
 int ofdm_tx(ofdm_plan_t plan, void* stream, const uint8_t* bits, uint64_t seed, int64_t sym0,
             int64_t n_sym, void* y, ofdm_stats* stats);

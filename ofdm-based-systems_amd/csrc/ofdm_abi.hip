@@ -117,6 +117,10 @@ struct ofdm_plan_s {
     // LUT has more than 256 entries, so the fused kernels stage no LUT and use the WideAxis table
     DevBuf wide;
     int max_bits, wide_plan;
+    // an MMSE plan whose response is exactly zero on some subcarrier: its equalised symbol there is an
+    // exact zero in every OFDM symbol, the tie AxisInfo::zero_i / zero_q decide -- every receiver
+    // launch of the plan takes the generic kernel, which applies them (RxArgs::zero_tie)
+    int zero_tie;
     size_t csize() const { return prec == OFDM_F32 ? 8 : 16; }
 };
 
@@ -179,7 +183,18 @@ int build_axis(const double* lut, int m, int lut_off, AxisInfo& ax, WideAxis& wi
     ax.lev0 = lev[0];
     ax.inv_step = inv_step;
     ax.side = side;
-    ax.hbits = b / 2;
+    ax.hbits = (int16_t)(b / 2);
+    // A component that is exactly zero lies on the boundary between the two central levels, and the
+    // origin ties between the four central points: the reference's argmin over |z - C_m| takes the
+    // first index (NNClassifier, constellation/models.py:19-27).  Read that decision off the LUT: the
+    // levels of the first point nearest the origin.  (The two points that share a row differ in
+    // their low index bits only and the two that share a column in their high bits only, so the
+    // first index of the four also decides each axis when only one component is zero.)
+    int i0 = 0;
+    for (int i = 1; i < m; ++i)
+        if (std::hypot(lut[2 * i], lut[2 * i + 1]) < std::hypot(lut[2 * i0], lut[2 * i0 + 1])) i0 = i;
+    ax.zero_i = (uint8_t)(std::find(lev.begin(), lev.end(), lut[2 * i0]) - lev.begin());
+    ax.zero_q = (uint8_t)(std::find(lev.begin(), lev.end(), lut[2 * i0 + 1]) - lev.begin());
     // (every level carries exactly one index pattern per axis: m = side^2 entries over side x side
     // consistent pairs, so iset / qset are permutations of [0, side) and invert)
     static_assert(kWideSide * kWideSide == kMaxOrder, "WideAxis holds the largest side");
@@ -492,6 +507,13 @@ int ofdm_plan_create(ofdm_plan_t* out, const ofdm_desc* d, void* stream) {
         HIPCHK(hipMemcpyAsync(&gs, g.p, sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         p->gain_mean = gs / p->n;
+        if (p->eq == OFDM_EQ_MMSE) {
+            std::vector<double> Hh(2 * (size_t)p->n);
+            HIPCHK(hipMemcpyAsync(Hh.data(), p->H64.p, 16 * (size_t)p->n, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            for (int k = 0; k < p->n; ++k)
+                if (Hh[2 * k] == 0.0 && Hh[2 * k + 1] == 0.0) p->zero_tie = 1;
+        }
     }
     HIPCHK(hipStreamSynchronize(s));
     *out = guard.release();
@@ -904,6 +926,7 @@ static int rx_args(const char* who, ofdm_plan_t p, const void* y, const double* 
     a.noise_on = noise_on;
     a.n_valid_bits = n_valid_bits;
     a.counters = counters;
+    a.zero_tie = p->zero_tie;
     *run = true;
     return OFDM_OK;
 }

@@ -378,16 +378,24 @@ __device__ __forceinline__ void load_twiddles(cpx<R>* lds, const cpx<R>* g) {
 
 // Per-LUT decision info for the separable square-QAM LUTs: LUT[i] = lev[ki] + j lev[kq]
 // with i = (qpat[kq] << hbits) | ipat[ki]; levels sorted ascending, uniform step.
+// zero_i / zero_q: the level a component that is exactly +-0 decides, per axis -- the tie between the
+// two central levels as the reference's first-index argmin breaks it (build_axis reads it off the LUT:
+// the level of LUT[argmin |C_m|] on each axis).  The operators and the generic fused kernels apply it
+// (slice_level); the throughput kernels never meet an exact zero (launchers: zero_tie).  The struct
+// keeps its 64 bytes: the throughput kernels stage it through registers.
 struct AxisInfo {
     double lev0;      // most negative level
     double inv_step;  // 1 / level spacing
     int32_t side;     // sqrt(M)
-    int32_t hbits;    // b / 2
+    int16_t hbits;    // b / 2
+    uint8_t zero_i;   // level of an I component that is exactly zero
+    uint8_t zero_q;   // level of a Q component that is exactly zero
     int32_t lut_off;  // offset of this LUT in the pool
     int32_t bits;     // b
     uint8_t ipat[16];
     uint8_t qpat[16];
 };
+static_assert(sizeof(AxisInfo) == 64, "AxisInfo is staged as 16 dwords");
 
 // The same decomposition for sides up to 64 (orders up to 4096), in a per-plan table of its own
 // beside AxisInfo: the throughput kernels stage AxisInfo through registers and never see a side
@@ -829,29 +837,40 @@ __device__ __forceinline__ uint32_t extract_w(const uint32_t* w, int o, int b) {
 }
 
 // Per-axis decision held in registers: ipat / qpat as 4-bit nibbles of a 64-bit word.
+// The level of one component (the operators' and the generic fused kernels' rounding slicer):
+// floor((u - lev0) * inv_step + 1/2) clamped to [0, smax].  The clamp comes before the conversion: on a
+// zero-forced null bin the level coordinate reaches 1e10 and more, outside int's range.  A component
+// that is exactly +-0 lies on the boundary between the two central levels, where the rounding of
+// lev0 * inv_step would decide; it takes `zero`, the level the reference's first-index argmin decides
+// (AxisInfo::zero_i / zero_q).
+template <typename R>
+__device__ __forceinline__ int slice_level(R u, R lev0, R inv_step, int smax, int zero) {
+    const R t = fmin(fmax((u - lev0) * inv_step + (R)0.5, (R)0), (R)smax);
+    return u == (R)0 ? zero : (int)floor(t);
+}
+
 template <typename R>
 struct Slicer {
     R lev0, inv_step;
-    int smax, hbits;
+    int smax, hbits, zero_i, zero_q;
     uint64_t ipat, qpat;
     __device__ void load(const AxisInfo& a) {
         lev0 = (R)a.lev0;
         inv_step = (R)a.inv_step;
         smax = a.side - 1;
         hbits = a.hbits;
+        zero_i = a.zero_i;
+        zero_q = a.zero_q;
         ipat = qpat = 0;
         for (int k = 0; k < a.side; ++k) {
             ipat |= (uint64_t)a.ipat[k] << (4 * k);
             qpat |= (uint64_t)a.qpat[k] << (4 * k);
         }
     }
-    __device__ __forceinline__ int level(R u) const {
-        int k = (int)floor((u - lev0) * inv_step + (R)0.5);
-        return min(max(k, 0), smax);
-    }
+    __device__ __forceinline__ int level(R u, int zero) const { return slice_level<R>(u, lev0, inv_step, smax, zero); }
     __device__ __forceinline__ uint32_t operator()(cpx<R> z) const {
-        const uint32_t i = (uint32_t)(ipat >> (4 * level(z.re))) & 15u;
-        const uint32_t q = (uint32_t)(qpat >> (4 * level(z.im))) & 15u;
+        const uint32_t i = (uint32_t)(ipat >> (4 * level(z.re, zero_i))) & 15u;
+        const uint32_t q = (uint32_t)(qpat >> (4 * level(z.im, zero_q))) & 15u;
         return (q << hbits) | i;
     }
 };
@@ -1468,17 +1487,13 @@ __device__ __forceinline__ f32x2 noise_table_entry(double sigma, int j) {
 
 // ------------------------------------------------------------------ constellation tables
 template <typename R>
-__device__ __forceinline__ int slice_axis(R u, const AxisInfo& a) {
-    R t = (u - (R)a.lev0) * (R)a.inv_step + (R)0.5;
-    int k = (int)floor(t);
-    k = k < 0 ? 0 : k;
-    k = k > a.side - 1 ? a.side - 1 : k;
-    return k;
+__device__ __forceinline__ int slice_axis(R u, const AxisInfo& a, int zero) {
+    return slice_level<R>(u, (R)a.lev0, (R)a.inv_step, a.side - 1, zero);
 }
 
 template <typename R>
 __device__ __forceinline__ uint32_t slice(cpx<R> z, const AxisInfo& a) {
-    const int ki = slice_axis<R>(z.re, a), kq = slice_axis<R>(z.im, a);
+    const int ki = slice_axis<R>(z.re, a, a.zero_i), kq = slice_axis<R>(z.im, a, a.zero_q);
     return ((uint32_t)a.qpat[kq] << a.hbits) | (uint32_t)a.ipat[ki];
 }
 
@@ -1487,7 +1502,7 @@ __device__ __forceinline__ uint32_t slice(cpx<R> z, const AxisInfo& a) {
 // (or a copy of it: ipat / qpat point at kWideSide bytes each).
 template <typename R>
 __device__ __forceinline__ uint32_t slice_wide(cpx<R> z, const AxisInfo& a, const uint8_t* ipat, const uint8_t* qpat) {
-    const int ki = slice_axis<R>(z.re, a), kq = slice_axis<R>(z.im, a);  // clamped to [0, side - 1]
+    const int ki = slice_axis<R>(z.re, a, a.zero_i), kq = slice_axis<R>(z.im, a, a.zero_q);  // in [0, side - 1]
     return ((uint32_t)qpat[kq] << a.hbits) | (uint32_t)ipat[ki];
 }
 

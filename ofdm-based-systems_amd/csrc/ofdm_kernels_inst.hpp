@@ -244,9 +244,11 @@ static inline bool adaptive_fast(const TxRxCommon& c) { return c.adaptive && c.u
 static inline bool fixed_fast(const TxRxCommon& c) {
     return !c.adaptive && (!c.nn || c.psk_m > 0) && (c.b % 2 == 0 || c.psk_m > 0);
 }
-// Philox bits and noise and no received-symbol tap: what every throughput receiver needs
+// Philox bits and noise, no received-symbol tap, and no exact zero whose tie the reference's first-index
+// rule decides (RxArgs::zero_tie: an MMSE plan with a null bin -- the throughput slicers round the origin
+// as their constants happen to, the generic kernel's apply the rule): what every throughput receiver needs
 static inline bool philox_streams(const RxArgs& a) {
-    return a.c.bits == nullptr && a.nr == nullptr && a.z_out == nullptr;
+    return a.c.bits == nullptr && a.nr == nullptr && a.z_out == nullptr && !a.zero_tie;
 }
 
 // The bench configs' shapes: complex128, OFDM with a cyclic prefix (or none) -- fixed 64-QAM at N = 1024
@@ -362,7 +364,8 @@ static hipError_t rx_one(const RxArgs& a, hipStream_t s) {
         // normals and no received-symbol tap
         // (MV: as the timed kernels -- compiled out of the fixed-QAM ones, and in the adaptive
         // kernel's instantiation, where FB = 1 forces SC-OFDM and zero padding off)
-        if (ref_shape<R, LOGN>(a.c) && a.nr != nullptr && a.z_out == nullptr)
+        // (and, as philox_streams, no tie at the origin to decide)
+        if (ref_shape<R, LOGN>(a.c) && a.nr != nullptr && a.z_out == nullptr && !a.zero_tie)
             return rx_eq<R, LOGN, ref_fb<R, LOGN>(), ref_fb<R, LOGN>() == 1, true>(a, s);
     }
     if constexpr (LOGN >= kFastMinLogN) {

@@ -194,6 +194,12 @@ struct RxArgs {
     int64_t z_keep;
     int flags;  // diagnostic ablation (OFDM_ABLATION builds, OFDM_ABLATE_RX): 1 no noise, 2 no FFT, 4 no bit staging,
                 // 8 no equalise/demap/compare, 16 no y load
+    // Host side only (the launchers read it, no kernel does; it sits in the padding behind `flags`, so the
+    // kernels' argument offsets are what they were): an MMSE plan with an exact zero in its response
+    // (the plan's zero_tie).  The equalised symbol of that subcarrier is an exact zero, whose decision is
+    // AxisInfo::zero_i / zero_q -- a tie only the generic kernel's slicers resolve, so no launcher gives
+    // such a call a throughput form (philox_streams, rx_one, rx_sweep_one).
+    int zero_tie;
     const WideAxis* wide;  // a plan with an order above 256 (generic kernel only): per-LUT level patterns
     // ofdm_rx_profile: the run's per-subcarrier record, int64[5][N] (ofdm_hip.h); read by k_rx_prof only
     int64_t* profile;

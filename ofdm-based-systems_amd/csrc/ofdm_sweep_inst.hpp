@@ -31,7 +31,8 @@ static hipError_t rx_sweep_launch(const RxSweepArgs& a, hipStream_t s) {
 template <typename R, int LOGN>
 static hipError_t rx_sweep_one(const RxSweepArgs& a, hipStream_t s) {
     if constexpr (ref_fb<R, LOGN>() > 1) {
-        if (bench_fixed_shape<ref_fb<R, LOGN>()>(a.r.c))
+        // (zero_tie: an MMSE plan with a null bin decides its exact zeros in the generic kernel, RxArgs)
+        if (bench_fixed_shape<ref_fb<R, LOGN>()>(a.r.c) && !a.r.zero_tie)
             return with_eq(a.r.c.eq, [&](auto eq) {
                 return rx_sweep_launch<R, LOGN, decltype(eq)::value, ref_fb<R, LOGN>()>(a, s);
             });

@@ -4,9 +4,9 @@ TEST INFRASTRUCTURE ONLY: pure Python + NumPy, no GPU, no package import.
 
 ``dispatch`` restates, for throughput mode (Philox bits and noise, no received-symbol tap), what
 ``csrc/ofdm_kernels_inst.hpp`` picks: ``tx_one`` / ``tx_fast`` / ``rx_one`` / ``rx_eq`` with
-``fixed_fast``, ``adaptive_fast`` and ``kFastMinLogN``, and the plan flags they read as
+``fixed_fast``, ``adaptive_fast``, ``philox_streams`` and ``kFastMinLogN``, and the plan flags they read as
 ``csrc/ofdm_abi.hip`` sets them (``separable``, ``upat``, ``psk_m``, ``zpad = zero padding and
-cp > 0``).  It returns the pair
+cp > 0``, ``zero_tie = MMSE and an exact zero in H``).  It returns the pair
 
     ("k_tx", R, LOGN, FB, LT, ZPW), ("k_rx", R, LOGN, EQ, FB, MV)
 
@@ -66,6 +66,9 @@ class Plan:
     modulator: str = "OFDM"   # "OFDM" | "SC"
     eq: str = "NONE"
     orders: Optional[tuple] = None
+    # the channel response is exactly zero on some subcarrier (RxArgs::zero_tie with MMSE): the
+    # receiver decides that subcarrier's exact zeros by the first-index rule, in the generic kernel
+    null_bin: bool = False
 
 
 def _separable(bits: int, scheme: str) -> bool:
@@ -120,6 +123,8 @@ def dispatch(p: Plan):
     # rx_one / rx_eq: complex64 compiles the modem variants into every receiver, complex128 keeps
     # them in kernels of their own; the adaptive receiver is rx_eq's default (MV)
     mv = True if (p.prec == F32 or fb == 1) else (p.modulator == "SC" or zpad)
+    if p.null_bin and p.eq == "MMSE":  # philox_streams: zero_tie keeps the receiver off the throughput forms
+        return tx, ("k_rx", R, logn, -1, 0, True)
     return tx, ("k_rx", R, logn, EQ_CODE[p.eq], fb, mv)
 
 
