@@ -412,6 +412,9 @@ int ofdm_rx_sweep(ofdm_plan_t plan, void* stream, const void* y, uint64_t seed, 
                   int64_t total_samples, const double* snr_db, int32_t n_snr, int64_t sym0, int64_t n_sym,
                   int64_t n_valid_bits, uint64_t* counters);
 
+/* ofdm_rx_sweep with the per-frame error record of every point: include/ofdm_hip_sweep_frames.h, an
+ * extension header of this ABI version (it declares one more entry point of the same library). */
+
 /* The fused link: transmit and receive symbols [sym0, sym0 + n_sym) in one kernel, without the kept
  * channel samples ever leaving the registers -- adds to `counters` what ofdm_tx(plan, stream, NULL, seed,
  * sym0, n_sym, y, ...) into a buffer followed by ofdm_rx(plan, stream, y, NULL, NULL, seed, stats,

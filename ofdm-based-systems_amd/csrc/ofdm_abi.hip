@@ -1,4 +1,4 @@
-// ofdm_abi.hip -- C ABI of libofdm_hip.so (include/ofdm_hip.h): plan management,
+// ofdm_abi.hip -- C ABI of libofdm_hip.so (include/ofdm_hip.h, ofdm_hip_sweep_frames.h): plan management,
 // argument validation, error reporting, and dispatch to the gfx950 kernels.
 //
 // A plan owns only constant tables (twiddles, LUTs, normalised CIR, equaliser
@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ofdm_hip.h"
+#include "ofdm_hip_sweep_frames.h"
 #include "ofdm_launch.hpp"
 
 using namespace ofdm;
@@ -956,6 +957,16 @@ static int frames_ok(const char* who, const RxFrames& fr, int64_t sym0, int64_t 
     }
     return (int)OFDM_OK;
 }
+// the 64-bit part of the frame index, done on the host once (RxFramesTail)
+static RxFramesTail frames_tail(const RxFrames& fr, int64_t sym0) {
+    RxFramesTail ft{};
+    ft.frames = (unsigned long long*)fr.frames;
+    ft.base = sym0 / fr.frame_len;
+    ft.n_frames = fr.n_frames;
+    ft.first = (uint32_t)std::min<int64_t>(fr.frame_len - sym0 % fr.frame_len, (int64_t)1 << 31);
+    ft.flen = (uint32_t)std::min<int64_t>(fr.frame_len, 0xFFFFFFFFll);
+    return ft;
+}
 // ofdm_rx_density's record and grid (ofdm_hip.h)
 struct RxDens {
     double lo, inv_w;
@@ -996,13 +1007,7 @@ static int rx_call(const char* who, ofdm_plan_t p, void* stream, const void* y, 
     a.wide = p->wide_plan ? (const WideAxis*)p->wide.p : nullptr;  // an order above 256: the wide slicer
     a.profile = profile;
     if (fr) {
-        // the 64-bit part of the frame index, done here once (RxFramesTail)
-        RxFramesTail ft{};
-        ft.frames = (unsigned long long*)fr->frames;
-        ft.base = sym0 / fr->frame_len;
-        ft.n_frames = fr->n_frames;
-        ft.first = (uint32_t)std::min<int64_t>(fr->frame_len - sym0 % fr->frame_len, (int64_t)1 << 31);
-        ft.flen = (uint32_t)std::min<int64_t>(fr->frame_len, 0xFFFFFFFFll);
+        const RxFramesTail ft = frames_tail(*fr, sym0);
         return checked(who, p, with_prec(p, [&](auto r) {
             return launch_rx_frames<decltype(r)>(p->logn, a, ft, (hipStream_t)stream);
         }));
@@ -1068,31 +1073,57 @@ int ofdm_rx_density(ofdm_plan_t p, void* stream, const void* y, const double* nr
                    n_sym, n_valid_bits, counters, z_out, z_keep, nullptr, nullptr, &dn);
 }
 
-int ofdm_rx_sweep(ofdm_plan_t p, void* stream, const void* y, uint64_t seed, const ofdm_stats* stats,
-                  int64_t total_samples, const double* snr_db, int32_t n_snr, int64_t sym0, int64_t n_sym,
-                  int64_t n_valid_bits, uint64_t* counters) {
+// ofdm_rx_sweep and ofdm_rx_sweep_frames (who; fr: the frame record of every point, or null -- without it
+// ofdm_rx_sweep, whose checks, arguments and launch are then what they were)
+static int sweep_call(const char* who, ofdm_plan_t p, void* stream, const void* y, uint64_t seed, const ofdm_stats* stats,
+                      int64_t total_samples, const double* snr_db, int32_t n_snr, int64_t sym0, int64_t n_sym,
+                      int64_t n_valid_bits, uint64_t* counters, const RxFrames* fr = nullptr) {
     const auto points_ok = [&] {
         if (n_snr < 1 || n_snr > OFDM_MAX_SWEEP_POINTS)
-            return fail(OFDM_E_INVALID, "ofdm_rx_sweep takes 1 to " + std::to_string(OFDM_MAX_SWEEP_POINTS) +
+            return fail(OFDM_E_INVALID, std::string(who) + " takes 1 to " + std::to_string(OFDM_MAX_SWEEP_POINTS) +
                                             " SNR points per call, got " + std::to_string(n_snr));
-        if (!snr_db) return fail(OFDM_E_INVALID, "bad argument to ofdm_rx_sweep");
+        if (!snr_db) return fail(OFDM_E_INVALID, std::string("bad argument to ") + who);
         for (int k = 0; k < n_snr; ++k)
             if (!std::isfinite(snr_db[k]))
-                return fail(OFDM_E_INVALID, "ofdm_rx_sweep: SNR point " + std::to_string(k) + " is not finite");
+                return fail(OFDM_E_INVALID, std::string(who) + ": SNR point " + std::to_string(k) + " is not finite");
         return (int)OFDM_OK;
     };
     RxSweepArgs a{};
     bool run;
     // (Philox streams, noise always on: no caller bits or normals)
-    const int rc = rx_args("ofdm_rx_sweep", p, y, nullptr, nullptr, seed, stats, total_samples, 1, nullptr, sym0, n_sym,
+    const int rc = rx_args(who, p, y, nullptr, nullptr, seed, stats, total_samples, 1, nullptr, sym0, n_sym,
                            n_valid_bits, counters, points_ok, a.r, &run);
     if (!run) return rc;
     a.n_snr = n_snr;
     for (int k = 0; k < n_snr; ++k) a.snr_lin[k] = std::pow(10.0, snr_db[k] / 10.0);  // (as ofdm_rx)
     a.r.snr_lin = a.snr_lin[0];
-    return checked("ofdm_rx_sweep", p, with_prec(p, [&](auto r) {
+    if (fr) {
+        const RxFramesTail ft = frames_tail(*fr, sym0);
+        return checked(who, p, with_prec(p, [&](auto r) {
+            return launch_rx_sweep_frames<decltype(r)>(p->logn, a, ft, (hipStream_t)stream);
+        }));
+    }
+    return checked(who, p, with_prec(p, [&](auto r) {
         return launch_rx_sweep<decltype(r)>(p->logn, a, (hipStream_t)stream);
     }));
+}
+
+int ofdm_rx_sweep(ofdm_plan_t p, void* stream, const void* y, uint64_t seed, const ofdm_stats* stats,
+                  int64_t total_samples, const double* snr_db, int32_t n_snr, int64_t sym0, int64_t n_sym,
+                  int64_t n_valid_bits, uint64_t* counters) {
+    return sweep_call("ofdm_rx_sweep", p, stream, y, seed, stats, total_samples, snr_db, n_snr, sym0, n_sym, n_valid_bits,
+                      counters);
+}
+
+int ofdm_rx_sweep_frames(ofdm_plan_t p, void* stream, const void* y, uint64_t seed, const ofdm_stats* stats,
+                         int64_t total_samples, const double* snr_db, int32_t n_snr, int64_t sym0, int64_t n_sym,
+                         int64_t n_valid_bits, uint64_t* counters, int64_t frame_len, int64_t n_frames,
+                         uint64_t* frames) {
+    // (n_frames: the rows of one point; the record holds n_snr times as many)
+    const RxFrames fr{frame_len, n_frames, frames};
+    if (const int rc = frames_ok("ofdm_rx_sweep_frames", fr, sym0, n_sym)) return rc;
+    return sweep_call("ofdm_rx_sweep_frames", p, stream, y, seed, stats, total_samples, snr_db, n_snr, sym0, n_sym,
+                      n_valid_bits, counters, &fr);
 }
 
 // ofdm_link, ofdm_link_sparse, ofdm_link_nscreen and ofdm_link_screen (screen: the kernel's, kLinkScreen*;

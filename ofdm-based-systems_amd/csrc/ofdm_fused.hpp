@@ -1539,4 +1539,27 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<
 #undef OFDM_RX_BODY_SWEEP
 }
 
+// The sweep receiver that also accumulates the per-frame error record of every point
+// (ofdm_rx_sweep_frames, ofdm_hip_sweep_frames.h: the definition): k_rx_sweep with k_rx_frames' frame block compiled
+// into the point loop.  There bes / ses are the symbol's counts at the point, so the block is what it
+// is in k_rx_frames -- the segment sum over the symbol's lanes, then one 64-bit integer atomic per
+// non-zero field from the segment's first lane -- into row pt * n_frames + frame of a point-major record.
+// counters[n_snr][2] stay the sweep's per-point pairs in lds.scnt: where a symbol is whole waves (N >= 1024)
+// the frame block's wave sum feeds them and the sweep's own 64-lane __shfl_xor sum is compiled out; where
+// several symbols share a wave the segment sums are not mixed and the sweep's own sum stays.
+// No LDS and no barrier beyond k_rx_sweep's, so its workgroup shapes, waves per SIMD and grid.  The frame
+// arguments are the trailing kernel parameter (RxFramesTail, as k_rx_frames'): RxSweepArgs and every
+// other receiver stay what they were.  Instantiated as k_rx_sweep is (ofdm_sweep_inst.hpp: one routing).
+template <typename R, int LOGN, int EQ, int FB, bool MV>
+__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<R, FB, LOGN, EQ, MV, true>())) void k_rx_sweep_frames(
+    RxSweepArgs sa, RxFramesTail ft) {
+    constexpr bool PROF = false, SWEEP = true, FRAMES = true, DENS = false, REF = false, WIDE = false;
+    const RxArgs& a = sa.r;  // (as k_rx_sweep)
+#define OFDM_RX_BODY_SWEEP
+#define OFDM_RX_BODY_FRAMES
+#include "ofdm_rx_body.hpp"
+#undef OFDM_RX_BODY_FRAMES
+#undef OFDM_RX_BODY_SWEEP
+}
+
 }  // namespace ofdm

@@ -205,9 +205,10 @@ struct RxArgs {
     int64_t* profile;
 };
 
-// ofdm_rx_frames: the frame record's arguments, a second kernel parameter behind RxArgs (k_rx_frames
-// only; every other receiver takes its arguments alone, as before).  The host does the 64-bit part of
-// the frame index: global symbol sym0 + sl (sl: the call-relative index, < 2^31) lies in frame
+// ofdm_rx_frames: the frame record's arguments, a second kernel parameter behind RxArgs (k_rx_frames, and
+// behind RxSweepArgs k_rx_sweep_frames, whose record is uint64[n_snr][n_frames][2] and n_frames the rows
+// of one point; every other receiver takes its arguments alone, as before).  The host does the 64-bit part
+// of the frame index: global symbol sym0 + sl (sl: the call-relative index, < 2^31) lies in frame
 //   base                              for sl < first,
 //   base + 1 + (sl - first) / flen    otherwise (a 32-bit division),
 // base = floor(sym0 / F), first = min(F - sym0 mod F, 2^31): the call's symbols before its first frame
@@ -331,6 +332,11 @@ hipError_t launch_rx_dens(int logn, const RxArgs& a, const RxDensTail& d, hipStr
 // the one-pass SNR sweep receiver (ofdm_sweep_inst.hpp)
 template <typename R>
 hipError_t launch_rx_sweep(int logn, const RxSweepArgs& a, hipStream_t s);
+
+// the sweep receiver with the per-frame error record of every point (ofdm_sweepframes_inst.hpp);
+// f.frames: device uint64[a.n_snr][f.n_frames][2]
+template <typename R>
+hipError_t launch_rx_sweep_frames(int logn, const RxSweepArgs& a, const RxFramesTail& f, hipStream_t s);
 
 // the fused link kernel (ofdm_link_inst.hpp; complex128 only); L: the plan's channel taps.
 // kNoFusedForm: the plan or the arguments have no fused form, nothing was launched

@@ -6,6 +6,9 @@
 // `RxDensTail dt` in scope): every equalised point is also binned into the density histogram in LDS.
 // FRAMES (k_rx_frames only, which defines OFDM_RX_BODY_FRAMES around its include and has its second
 // argument `RxFramesTail ft` in scope): each symbol's counts are also added to its frame's pair.
+// FRAMES and SWEEP (k_rx_sweep_frames only, which defines both macros and has `sa` and `ft` in scope): the
+// frame block runs inside the point loop, where bes / ses are the symbol's at the point, and adds them
+// to the point's rows of a point-major record, frames[pt][frame][2].
 // SWEEP (k_rx_sweep only, which defines OFDM_RX_BODY_SWEEP around its include and has its argument
 // `RxSweepArgs sa` in scope, `a` being sa.r): every symbol is received once per SNR
 // point, the point loop opened and closed under that macro so that the other kernels' text has no loop.
@@ -14,10 +17,15 @@
                   "the profile: the generic kernel, or a complex128 cyclic-prefix OFDM QAM throughput receiver");
     static_assert(!SWEEP || (!REF && !WIDE && !PROF && (FB == 0 || (sizeof(R) == 8 && FB > 1 && !(FB & 1) && !MV))),
                   "the sweep: the generic kernel, or a complex128 cyclic-prefix OFDM fixed-QAM throughput receiver");
-#ifdef OFDM_RX_BODY_FRAMES
+#if defined(OFDM_RX_BODY_FRAMES) && defined(OFDM_RX_BODY_SWEEP)
+    // (k_rx_sweep_frames, the one kernel with both: the sweep's own condition above holds for it)
+    static_assert(FRAMES && SWEEP, "the frame record of a sweep: k_rx_sweep_frames defines both macros around its include");
+#define OFDM_RX_FRAME_ROW(f) ((int64_t)pt * ft.n_frames + (f))  // point-major: the point's rows
+#elif defined(OFDM_RX_BODY_FRAMES)
     static_assert(FRAMES && !REF && !PROF && !SWEEP &&
                       (FB == 0 || (sizeof(R) == 8 && (FB == 1 || !(FB & 1)) && (FB == 1 || !MV))),
                   "the frame record: the generic kernel, or a complex128 cyclic-prefix OFDM QAM throughput receiver");
+#define OFDM_RX_FRAME_ROW(f) (f)
 #else
     static_assert(!FRAMES, "k_rx_frames defines OFDM_RX_BODY_FRAMES around its include");
 #endif
@@ -694,13 +702,22 @@
                 if constexpr (SEG == 64)
                     v = (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 32);
                 if ((threadIdx.x & (SEG - 1)) == 0 && v) {
+#ifdef OFDM_RX_BODY_SWEEP
+                    // k_rx_sweep_frames, a symbol of whole waves: v is the wave's sum of the symbol at this
+                    // point, which the sweep's own wave sum below would form again -- the workgroup's pair of
+                    // the point gets it from here.  (Segments of several symbols per wave: left to that sum.)
+                    if constexpr (SEG == 64) {
+                        atomicAdd(&lds.scnt[2 * pt], (unsigned long long)(v & 0xFFFFu));
+                        atomicAdd(&lds.scnt[2 * pt + 1], (unsigned long long)(v >> 16));
+                    }
+#endif
                     const uint32_t rel = (uint32_t)sl;
                     const int64_t f = ft.base + (rel < ft.first ? 0 : 1 + (int64_t)((rel - ft.first) / ft.flen));
                     // a memory-safety guard only, never taken: the ABI (frames_ok, the one check of the frame
                     // arguments) refuses a record too short for the call's last symbol before any launch
                     if (f < ft.n_frames) {
-                        if (v & 0xFFFFu) atomicAdd(ft.frames + 2 * f, (unsigned long long)(v & 0xFFFFu));
-                        if (v >> 16) atomicAdd(ft.frames + 2 * f + 1, (unsigned long long)(v >> 16));
+                        if (v & 0xFFFFu) atomicAdd(ft.frames + 2 * OFDM_RX_FRAME_ROW(f), (unsigned long long)(v & 0xFFFFu));
+                        if (v >> 16) atomicAdd(ft.frames + 2 * OFDM_RX_FRAME_ROW(f) + 1, (unsigned long long)(v >> 16));
                     }
                 }
             }
@@ -709,13 +726,16 @@
 #ifdef OFDM_RX_BODY_SWEEP
         // this symbol's counts at this point (a lane's: <= 128 bit and 16 symbol errors, so both fit one
         // word through the wave's sum) into the workgroup's pair of the point
+        // (k_rx_sweep_frames with a symbol of whole waves: the frame block has added the wave's sum)
         {
-            unsigned long long v = be | (se << 32);
+            if constexpr (!(FRAMES && TPS >= 64)) {
+                unsigned long long v = be | (se << 32);
 #pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-            if ((threadIdx.x & 63) == 0 && v) {
-                atomicAdd(&lds.scnt[2 * pt], v & 0xFFFFFFFFull);
-                atomicAdd(&lds.scnt[2 * pt + 1], v >> 32);
+                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+                if ((threadIdx.x & 63) == 0 && v) {
+                    atomicAdd(&lds.scnt[2 * pt], v & 0xFFFFFFFFull);
+                    atomicAdd(&lds.scnt[2 * pt + 1], v >> 32);
+                }
             }
             be = se = 0;
         }
@@ -788,3 +808,6 @@
         });
     }
 #undef OFDM_RX_SNR_LIN
+#ifdef OFDM_RX_BODY_FRAMES
+#undef OFDM_RX_FRAME_ROW
+#endif

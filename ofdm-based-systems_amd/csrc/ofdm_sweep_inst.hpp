@@ -11,8 +11,10 @@ namespace ofdm {
 // throughput receiver's k_rx_sweep, by equaliser.  Everything else takes the generic kernel's (EQ = -1,
 // FB = 0): complex64, SC-OFDM, zero padding, PSK, N < 64, adaptive plans (one plan for every point:
 // adaptive loading re-derived per SNR is a different plan per point and not a sweep).
-template <typename R, int LOGN, int EQ, int FB>
-static hipError_t rx_sweep_launch(const RxSweepArgs& a, hipStream_t s) {
+// tail: nothing (k_rx_sweep), or the frame record's RxFramesTail (k_rx_sweep_frames,
+// ofdm_sweepframes_inst.hpp) -- one routing, one layout and one grid for both.
+template <typename R, int LOGN, int EQ, int FB, typename... T>
+static hipError_t rx_sweep_launch(const RxSweepArgs& a, hipStream_t s, const T&... tail) {
     constexpr bool MV = FB == 0;  // (the generic kernel as rx_one launches it; compiled out of the fixed-QAM ones)
     constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV, true>();
     const TxRxCommon& c = a.r.c;
@@ -20,29 +22,37 @@ static hipError_t rx_sweep_launch(const RxSweepArgs& a, hipStream_t s) {
     rx_carve<R, LOGN, EQ, FB, MV, true>(lds, c.words_per_sym, rx_tts<R, LOGN, FB>(c.scm), 0, a.n_snr);
     if (lds.bytes + rx_static_lds<R, FB>() > kLdsPerCu) {
         // (a layout that does not fit: the generic kernel, which is the last resort)
-        if constexpr (FB > 0) return rx_sweep_launch<R, LOGN, -1, 0>(a, s);
+        if constexpr (FB > 0) return rx_sweep_launch<R, LOGN, -1, 0>(a, s, tail...);
         else return kLdsOverflow;
     }
     // Every workgroup builds a table per point and ends with an atomic pair per point: two rounds of
     // the resident workgroups (as the profile's launcher)
-    return rx_go<BLK, Geo<LOGN, BLK>::SPB>(k_rx_sweep<R, LOGN, EQ, FB, MV>, lds.bytes, 2, c.n_sym, a, s);
+    if constexpr (sizeof...(T) == 0)
+        return rx_go<BLK, Geo<LOGN, BLK>::SPB>(k_rx_sweep<R, LOGN, EQ, FB, MV>, lds.bytes, 2, c.n_sym, a, s);
+    else
+        return rx_go<BLK, Geo<LOGN, BLK>::SPB>(k_rx_sweep_frames<R, LOGN, EQ, FB, MV>, lds.bytes, 2, c.n_sym, a, s, tail...);
 }
 
-template <typename R, int LOGN>
-static hipError_t rx_sweep_one(const RxSweepArgs& a, hipStream_t s) {
+template <typename R, int LOGN, typename... T>
+static hipError_t rx_sweep_one(const RxSweepArgs& a, hipStream_t s, const T&... tail) {
     if constexpr (ref_fb<R, LOGN>() > 1) {
         // (zero_tie: an MMSE plan with a null bin decides its exact zeros in the generic kernel, RxArgs)
         if (bench_fixed_shape<ref_fb<R, LOGN>()>(a.r.c) && !a.r.zero_tie)
             return with_eq(a.r.c.eq, [&](auto eq) {
-                return rx_sweep_launch<R, LOGN, decltype(eq)::value, ref_fb<R, LOGN>()>(a, s);
+                return rx_sweep_launch<R, LOGN, decltype(eq)::value, ref_fb<R, LOGN>()>(a, s, tail...);
             });
     }
-    return rx_sweep_launch<R, LOGN, -1, 0>(a, s);
+    return rx_sweep_launch<R, LOGN, -1, 0>(a, s, tail...);
+}
+
+// the points and the plan a sweep launch takes (launch_rx_sweep, launch_rx_sweep_frames)
+static inline bool rx_sweep_args_ok(const RxSweepArgs& a) {
+    return a.n_snr >= 1 && a.n_snr <= OFDM_MAX_SWEEP_POINTS && a.r.wide == nullptr;
 }
 
 template <typename R>
 hipError_t launch_rx_sweep(int logn, const RxSweepArgs& a, hipStream_t s) {
-    if (a.n_snr < 1 || a.n_snr > OFDM_MAX_SWEEP_POINTS || a.r.wide != nullptr) return hipErrorInvalidValue;
+    if (!rx_sweep_args_ok(a)) return hipErrorInvalidValue;
     return with_logn(logn, [&](auto l) { return rx_sweep_one<R, decltype(l)::value>(a, s); });
 }
 

@@ -147,6 +147,13 @@ SIGNATURES = {
     "ofdm_tx_clip": (ctypes.c_int, [_VP, _VP, _VP, _U64, _I64, _I64, _VP, _VP, _F64, _VP]),
 }
 
+# (name, restype, argtypes) -- mirrors include/ofdm_hip_sweep_frames.h, the extension header of ABI 6: the
+# entry points the library exports beside those of ofdm_hip.h (SIGNATURES stays that header's mirror)
+EXTENSION_SIGNATURES = {
+    # (ofdm_rx_sweep's arguments, frame_len, n_frames, frames: uint64[n_snr][n_frames][2])
+    "ofdm_rx_sweep_frames": (ctypes.c_int, SIGNATURES["ofdm_rx_sweep"][1] + [_I64, _I64, _VP]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()
 
@@ -157,14 +164,15 @@ def lib_path() -> str:
 
 def build_id() -> str:
     """Identity of the kernel sources the library is built from: sha256 (16 hex digits) over the
-    HIP sources, the C-ABI header and the Makefile.  Profiles record it (profiles/pmc_summary.json)
+    HIP sources, the C-ABI headers and the Makefile.  Profiles record it (profiles/pmc_summary.json)
     so that bench.py reports PMC traffic only for the build it was measured on."""
     import hashlib
 
     pkg = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # ofdm-based-systems_amd/
     root = os.path.dirname(pkg)
     files = sorted(os.path.join(pkg, "csrc", f) for f in os.listdir(os.path.join(pkg, "csrc")))
-    files += [os.path.join(root, "include", "ofdm_hip.h"), os.path.join(pkg, "Makefile")]
+    files += [os.path.join(root, "include", "ofdm_hip.h"), os.path.join(root, "include", "ofdm_hip_sweep_frames.h"),
+              os.path.join(pkg, "Makefile")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode())
@@ -184,7 +192,7 @@ def load_library() -> ctypes.CDLL:
                 f"{_LIB_PATH} is missing: build it with `make -C ofdm-based-systems_amd` "
                 "or __graft_entry__.build()")
         handle = ctypes.CDLL(_LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **EXTENSION_SIGNATURES}.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

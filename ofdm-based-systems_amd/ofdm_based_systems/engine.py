@@ -35,7 +35,9 @@ N = 1024, fixed 64-QAM, cyclic-prefix OFDM, flat channel, no equaliser -- a Phil
 with no y in HBM at all and the same results bit for bit.
 
 SNR sweeps: :meth:`LinkEngine.run_sweep` transmits once and receives at every SNR of a list in one
-pass (ofdm_rx_sweep); point k is ``run(n_sym, snr_k, seed=seed)``.
+pass (ofdm_rx_sweep); point k is ``run(n_sym, snr_k, seed=seed)``.  :meth:`LinkEngine.run_frame_sweep`
+does the same with the per-frame error record of every point (ofdm_rx_sweep_frames): point k is
+``run(n_sym, snr_k, seed=seed, frame_symbols=F)`` -- an FER-versus-SNR curve from one transmit.
 
 Clipping: ``LinkEngine(..., clip_db=...)`` limits the envelope of the modulated samples at that level
 above the nominal sample power (ofdm_tx_clip: a soft limiter directly after the IFFT, before the guard
@@ -503,13 +505,22 @@ class LinkEngine:
         else:
             B.check(self._lib.ofdm_rx_profile(*args, B.ptr(profile)))
 
-    def rx_sweep(self, stream, y, seed, stats, total_samples, snr_dbs, sym0, n_sym, n_valid, counters):
+    def rx_sweep(self, stream, y, seed, stats, total_samples, snr_dbs, sym0, n_sym, n_valid, counters,
+                 frames=None, frame_symbols=None):
         """ofdm_rx_sweep: the receiver at every SNR of ``snr_dbs`` (at most B.MAX_SWEEP_POINTS, a host
-        list copied at the call) over the same y; counters: device int64 [len(snr_dbs)][2], accumulated."""
+        list copied at the call) over the same y; counters: device int64 [len(snr_dbs)][2], accumulated.
+        With a frame record (``frames``: device int64 [len(snr_dbs)][n_frames][2], the points' rows of
+        the whole run, contiguous; ``frame_symbols`` OFDM symbols per frame) ofdm_rx_sweep_frames."""
+        if frames is not None and (frames.dim() != 3 or frames.shape[0] != len(snr_dbs) or frames.shape[2] != 2
+                                   or not frames.is_contiguous()):
+            raise ValueError("rx_sweep: the frame record is not a contiguous int64 [len(snr_dbs)][n_frames][2]")
         snrs = (ctypes.c_double * len(snr_dbs))(*[float(q) for q in snr_dbs])
-        B.check(self._lib.ofdm_rx_sweep(self.plan.handle, stream, B.ptr(y), int(seed), B.ptr(stats),
-                                        int(total_samples), snrs, len(snr_dbs), int(sym0), int(n_sym),
-                                        int(n_valid), B.ptr(counters)))
+        args = (self.plan.handle, stream, B.ptr(y), int(seed), B.ptr(stats), int(total_samples), snrs, len(snr_dbs),
+                int(sym0), int(n_sym), int(n_valid), B.ptr(counters))
+        if frames is None:
+            B.check(self._lib.ofdm_rx_sweep(*args))
+        else:
+            B.check(self._lib.ofdm_rx_sweep_frames(*args, int(frame_symbols), int(frames.shape[1]), B.ptr(frames)))
 
     def link(self, stream, seed, stats, total_samples, snr_db, noise_on, sym0, n_sym, n_valid, counters):
         """ofdm_link: transmit and receive symbols [sym0, sym0 + n_sym) in one kernel, y never leaving
@@ -885,36 +896,81 @@ class LinkEngine:
         counts do not depend on the batching, the rank count, the order of the list or how it is split.
 
         Not taken: caller bits or normals, orders above 256, a profile, a frame record
-        (``frame_symbols``: ValueError), a density record (``density``: ValueError), a received-symbol
-        tap, and a plan per point (adaptive loading re-derived per SNR)."""
+        (``frame_symbols``: ValueError -- :meth:`run_frame_sweep_async` is the sweep with one), a density
+        record (``density``: ValueError), a received-symbol tap, and a plan per point (adaptive loading
+        re-derived per SNR)."""
         if density is not None:
             raise ValueError("run_sweep with density: the sweep receiver keeps no density record "
                              "(the density inside k_rx_sweep is not built); use run per point")
         if frame_symbols is not None:
-            raise ValueError("run_sweep with frame_symbols: the sweep receiver keeps no frame record "
-                             "(frames inside k_rx_sweep are not built); use run per point")
+            raise ValueError("run_sweep with frame_symbols: run_sweep keeps no frame record; the sweep with "
+                             "the record of every point is run_frame_sweep / run_frame_sweep_async")
+        return self._sweep_async("run_sweep", n_sym, snr_dbs, None, seed=seed, group=group, y_budget=y_budget,
+                                 batch=batch, n_valid_bits=n_valid_bits, events=events)
+
+    def run_frame_sweep(self, n_sym: int, snr_dbs, frame_symbols: int, **kw) -> list:
+        """An FER curve from one transmit: :meth:`run` with ``frame_symbols`` at every SNR of ``snr_dbs``
+        (see :meth:`run_frame_sweep_async`), one LinkStats per point in the order given."""
+        return self.run_frame_sweep_async(n_sym, snr_dbs, frame_symbols, **kw).result()
+
+    def run_frame_sweep_async(self, n_sym: int, snr_dbs, frame_symbols: int, *, seed: int = 0, group=None,
+                              y_budget: int = DEFAULT_Y_BUDGET, batch: Optional[int] = None,
+                              n_valid_bits: Optional[int] = None, events: Optional[list] = None) -> "PendingSweep":
+        """:meth:`run_sweep_async` with the per-frame error record of every point: point k is
+        ``run(n_sym, snr_dbs[k], seed=seed, frame_symbols=F)`` -- its counters as :meth:`run_sweep`
+        gives them, and ``.frames`` the :class:`FrameStats` that run builds, with the same
+        ``n_valid_bits`` handling -- from one transmit (``ofdm_rx_sweep_frames``).
+
+        The record is int64 [K][ceil(n_sym / F)][2], point-major, behind the [K][2] counters (and the
+        clip record) in the one buffer the asynchronous all-reduce carries; every batch and every rank
+        adds its own symbols' counts -- integers, so the record does not depend on the batching, the
+        rank count, the order of the list, how a list longer than B.MAX_SWEEP_POINTS is split into
+        launches (each takes the contiguous rows of its points), or whether a frame straddles any of
+        those.  Events are named "ofdm_rx_sweep_frames".
+
+        ValueError before any launch: a bad F or too many frames (:func:`frame_count`), more than
+        B.MAX_FRAMES rows over all points (the 256 MiB cap on the whole record), an empty list, a
+        non-finite point; otherwise what :meth:`run_sweep_async` does not take is not taken here."""
+        return self._sweep_async("run_frame_sweep", n_sym, snr_dbs, frame_symbols, seed=seed, group=group,
+                                 y_budget=y_budget, batch=batch, n_valid_bits=n_valid_bits, events=events)
+
+    def _sweep_async(self, who: str, n_sym: int, snr_dbs, frame_symbols, *, seed, group, y_budget, batch,
+                     n_valid_bits, events) -> "PendingSweep":
+        """run_sweep_async (``frame_symbols`` None) and run_frame_sweep_async: one schedule."""
+        n_frames = 0 if frame_symbols is None else frame_count(n_sym, frame_symbols)
         snrs = [float(q) for q in snr_dbs]
         if not snrs:
-            raise ValueError("run_sweep needs at least one SNR point")
+            raise ValueError(f"{who} needs at least one SNR point")
         if not all(math.isfinite(q) for q in snrs):
-            raise ValueError("run_sweep needs finite SNR points")
+            raise ValueError(f"{who} needs finite SNR points")
+        K = len(snrs)
+        if K * n_frames > B.MAX_FRAMES:
+            raise ValueError(f"{who}: frame_symbols = {frame_symbols} gives {n_frames} frames at each of {K} SNR "
+                             f"points, {K * n_frames} rows, above the cap of {B.MAX_FRAMES} (2^24 rows, a 256 MiB "
+                             "record); use longer frames, shorter runs or fewer points per sweep")
         r = self._share(n_sym, group, n_valid_bits)
         stats = new_stats(r.dev)
-        # the [K][2] counters, and behind them the clip record: one buffer, one all-reduce
+        # the [K][2] counters, and behind them the clip record and the [K][n_frames][2] frame record: one
+        # buffer, one all-reduce (every rank adds its own symbols' counts into the whole run's record)
         nclip = 0 if self.clip_a2 is None else 2
-        acc = torch.zeros(2 * len(snrs) + nclip, dtype=torch.int64, device=r.dev)
-        counters = acc[:2 * len(snrs)].view(len(snrs), 2)
-        clip = acc[2 * len(snrs):] if nclip else None
+        acc = torch.zeros(2 * K + nclip + 2 * K * n_frames, dtype=torch.int64, device=r.dev)
+        counters = acc[:2 * K].view(K, 2)
+        clip = acc[2 * K:2 * K + nclip] if nclip else None
+        frec = acc[2 * K + nclip:].view(K, n_frames, 2) if n_frames else None
+        rx_name = "ofdm_rx_sweep_frames" if n_frames else "ofdm_rx_sweep"
 
         def receive(y, sym0, n, resident):  # (timed per launch on either path)
-            for k0 in range(0, len(snrs), B.MAX_SWEEP_POINTS):
+            for k0 in range(0, K, B.MAX_SWEEP_POINTS):
                 k1 = k0 + B.MAX_SWEEP_POINTS
-                self._timed(events, "ofdm_rx_sweep", n, lambda: self.rx_sweep(
-                    r.stream, y, seed, stats, r.samples, snrs[k0:k1], sym0, n, r.n_valid, counters[k0:k1]))
+                # (rx_sweep without a frame record is called as before)
+                fkw = {"frames": frec[k0:k1], "frame_symbols": int(frame_symbols)} if n_frames else {}
+                self._timed(events, rx_name, n, lambda: self.rx_sweep(
+                    r.stream, y, seed, stats, r.samples, snrs[k0:k1], sym0, n, r.n_valid, counters[k0:k1], **fkw))
 
         done, work = self._schedule(r, seed, None, stats, receive, acc, group=group, y_budget=y_budget,
                                     batch=batch, events=events, clip=clip)
-        return PendingSweep(n_sym, r.samples, stats, counters, done, work, clip=clip, clip_db=self.clip_db)
+        return PendingSweep(n_sym, r.samples, stats, counters, done, work, clip=clip, clip_db=self.clip_db,
+                            frames=frec, frame_info=(int(frame_symbols), self.bps, r.n_valid) if n_frames else None)
 
     def lane_streams(self, lanes: int) -> list:
         """The current stream and lanes - 1 more, kept per engine (their allocator pools persist:
@@ -1100,11 +1156,15 @@ class PendingLink(_Pending):
 
 class PendingSweep(_Pending):
     """Device-side results of one :meth:`LinkEngine.run_sweep_async` call: the [K][2] counters and
-    the run's one statistics record."""
+    the run's one statistics record; of :meth:`LinkEngine.run_frame_sweep_async` also the
+    [K][n_frames][2] frame record."""
 
-    def __init__(self, n_sym, samples, stats, counters, done=None, work=None, clip=None, clip_db=None):
+    def __init__(self, n_sym, samples, stats, counters, done=None, work=None, clip=None, clip_db=None,
+                 frames=None, frame_info=None):
         self.n_sym, self.samples = n_sym, samples
         self.clip, self.clip_db = clip, clip_db
+        # the points' frame records (device int64 [K][n_frames][2]) and (F, bits per OFDM symbol, bits compared)
+        self.frames, self.frame_info = frames, frame_info
         self.stats, self.counters = stats, counters
         self.done, self.work = done, work
 
@@ -1113,5 +1173,13 @@ class PendingSweep(_Pending):
         power / PAPR fields."""
         self._wait()
         shared = self._statistics()
-        return [LinkStats(bit_errors=int(c[0]), symbol_errors=int(c[1]), **shared)
-                for c in self.counters.cpu().numpy()]
+        cnt = self.counters.cpu().numpy()
+        if self.frames is None:
+            return [LinkStats(bit_errors=int(c[0]), symbol_errors=int(c[1]), **shared) for c in cnt]
+        F, bps, n_valid = self.frame_info
+        rec = self.frames.cpu().numpy().astype(np.int64)[:, :-(-self.n_sym // F)]  # (as PendingLink.result)
+        return [LinkStats(bit_errors=int(c[0]), symbol_errors=int(c[1]),
+                          frames=FrameStats(frame_symbols=F, n_symbols=self.n_sym, bits_per_symbol=bps,
+                                            bit_errors=p[:, 0].copy(), symbol_errors=p[:, 1].copy(),
+                                            n_valid_bits=n_valid), **shared)
+                for c, p in zip(cnt, rec)]

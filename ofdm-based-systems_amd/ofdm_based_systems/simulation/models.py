@@ -316,7 +316,26 @@ class Simulation:
         Raises ValueError unless the simulations differ only in ``snr_db``, use
         ``rng_mode='philox'``, are FIXED mode with the built-in strategies and AWGN, and have
         ``received_symbols_keep == 0`` and no ``subcarrier_profile`` (the sweep receiver has no
-        caller streams, no plan per point, no received-symbol tap and no profile)."""
+        caller streams, no plan per point, no received-symbol tap and no profile), or if they set
+        ``frame_symbols`` (:meth:`run_frame_sweep` is the sweep with the frame record)."""
+        return cls._sweep("run_sweep", simulations, frames=False)
+
+    @classmethod
+    def run_frame_sweep(cls, simulations: List["Simulation"]) -> List[Dict[str, Any]]:
+        """:meth:`run_sweep` for simulations with a common ``frame_symbols``: the results of
+        ``[s.run() for s in simulations]`` -- the frame keys ``frame_symbols``, ``num_frames``,
+        ``frame_errors``, ``frame_error_rate``, ``ber_std_error`` and ``bit_errors_per_frame`` among them
+        -- from ONE engine frame sweep (LinkEngine.run_frame_sweep): a frame-error-rate curve from one
+        transmit.  ``transmission_time_ms`` is the whole sweep's.
+
+        Raises ValueError for what :meth:`run_sweep` refuses, except that ``frame_symbols`` must be set;
+        ``constellation_density``, ``subcarrier_profile`` and a received-symbol tap are still refused."""
+        return cls._sweep("run_frame_sweep", simulations, frames=True)
+
+    @classmethod
+    def _sweep(cls, who: str, simulations, frames: bool) -> List[Dict[str, Any]]:
+        """run_sweep (``frames`` False) and run_frame_sweep: the checks, and one engine sweep feeding
+        every simulation's _run."""
         sims = list(simulations)
         if not sims:
             return []
@@ -330,23 +349,25 @@ class Simulation:
         for s in sims[1:]:
             for key, val in vars(s).items():
                 if key != "snr_db" and not same(val, first[key]):
-                    raise ValueError(f"run_sweep: the simulations differ in more than snr_db ({key})")
+                    raise ValueError(f"{who}: the simulations differ in more than snr_db ({key})")
         s0 = sims[0]
         if s0.rng_mode != "philox":
-            raise ValueError("run_sweep needs rng_mode='philox' (the sweep receiver generates its streams)")
+            raise ValueError(f"{who} needs rng_mode='philox' (the sweep receiver generates its streams)")
         builtin = (s0._builtin_strategies()
                    and cls.NOISE_SCHEME_MAPPERS.get(s0.noise_scheme, AWGNoiseModel) is AWGNoiseModel)
         if s0.adaptive_modulation_mode != AdaptiveModulationMode.FIXED or not builtin:
-            raise ValueError("run_sweep needs FIXED mode with the built-in modulators, prefixes, constellations "
+            raise ValueError(f"{who} needs FIXED mode with the built-in modulators, prefixes, constellations "
                              "and AWGN (adaptive loading is a different plan per SNR)")
         if s0.received_symbols_keep != 0 or s0.subcarrier_profile:
-            raise ValueError("run_sweep needs received_symbols_keep=0 and no subcarrier_profile")
-        if s0.frame_symbols is not None:
-            raise ValueError("run_sweep with frame_symbols: the sweep receiver keeps no frame record; run the "
-                             "simulations one by one")
+            raise ValueError(f"{who} needs received_symbols_keep=0 and no subcarrier_profile")
+        if s0.frame_symbols is not None and not frames:
+            raise ValueError("run_sweep with frame_symbols: run_sweep keeps no frame record; the sweep with the "
+                             "record of every point is run_frame_sweep")
+        if s0.frame_symbols is None and frames:
+            raise ValueError("run_frame_sweep needs frame_symbols set on the simulations (without it: run_sweep)")
 
         if s0.constellation_density is not None:
-            raise ValueError("run_sweep with constellation_density: the sweep receiver keeps no density record; "
+            raise ValueError(f"{who} with constellation_density: the sweep receiver keeps no density record; "
                              "run the simulations one by one")
 
         swept: List[Any] = []  # the engine sweep's LinkStats, filled by the first simulation
@@ -354,9 +375,11 @@ class Simulation:
         def link(k):
             def stats(make_engine, n_sym, seed, valid_bits):
                 if not swept:
-                    swept.extend(make_engine().run_sweep(
-                        n_sym, [s.snr_db for s in sims], seed=seed, group=s0.process_group,
-                        batch=s0.batch_symbols, n_valid_bits=valid_bits))
+                    kw = dict(seed=seed, group=s0.process_group, batch=s0.batch_symbols, n_valid_bits=valid_bits)
+                    snrs = [s.snr_db for s in sims]
+                    eng = make_engine()
+                    swept.extend(eng.run_frame_sweep(n_sym, snrs, s0.frame_symbols, **kw) if frames
+                                 else eng.run_sweep(n_sym, snrs, **kw))
                 return swept[k]
             return stats
 
