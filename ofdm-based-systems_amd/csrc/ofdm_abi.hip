@@ -286,11 +286,10 @@ hipError_t with_prec(ofdm_plan_t p, F f) {
 }
 
 // The generic fused kernel's LDS layout for this shape exceeds a CU's (launcher: kLdsOverflow).
-// (lds_extra: what the entry point being served adds to the receiver's layout, named in the message --
-// ofdm_rx_density's histogram, set around its launch -- and empty otherwise)
-thread_local std::string lds_extra;
-int lds_overflow(ofdm_plan_t p, const char* who) {
-    return fail(OFDM_E_INVALID, std::string(who) + ": the shape" + lds_extra + " does not fit the LDS of a compute unit (n_fft " +
+// (extra: what the entry point being served adds to the receiver's layout, named in the message --
+// ofdm_rx_density's histogram -- and empty otherwise)
+int lds_overflow(ofdm_plan_t p, const char* who, const std::string& extra) {
+    return fail(OFDM_E_INVALID, std::string(who) + ": the shape" + extra + " does not fit the LDS of a compute unit (n_fft " +
                                     std::to_string(p->n) + ", " + (p->prec == OFDM_F32 ? "complex64" : "complex128") +
                                     ", prefix " + std::to_string(p->cp) + ", " + std::to_string(p->L) + " taps, " +
                                     std::to_string(p->bps) + " bits per OFDM symbol, LUT pool " +
@@ -300,10 +299,10 @@ int lds_overflow(ofdm_plan_t p, const char* who) {
 // A launcher's answer as entry point `who`'s: the one place that translates the launchers' verdicts
 // (ofdm_launch.hpp; no HIP call can return one) -- bad arguments, each naming its reason; kNotInBuild is
 // a dispatch that reached a shape an OFDM_AB_ONLY experiment build does not instantiate -- and reports
-// any other failure as a HIP error under the entry point's name.
-int checked(const char* who, ofdm_plan_t p, hipError_t e) {
+// any other failure as a HIP error under the entry point's name.  (layout_extra: lds_overflow's)
+int checked(const char* who, ofdm_plan_t p, hipError_t e, const std::string& layout_extra = {}) {
     if (e == hipSuccess) return OFDM_OK;
-    if (e == kLdsOverflow) return lds_overflow(p, who);
+    if (e == kLdsOverflow) return lds_overflow(p, who, layout_extra);
     if (e == kNoFusedForm) return fail(OFDM_E_INVALID, "ofdm_link: no fused form for this plan");
     if (kAbOnly && e == kNotInBuild)
         return fail(OFDM_E_INVALID, std::string(who) + ": kernel not in this build (an OFDM_AB_ONLY variant "
@@ -987,14 +986,15 @@ static int dens_ok(const char* who, const RxDens& d, int n_fft) {
                   ") is not 0 <= k_lo < k_hi <= n_fft" + (n_fft > 0 ? " = " + std::to_string(n_fft) : std::string()));
     return (int)OFDM_OK;
 }
-// ofdm_rx, ofdm_rx_profile, ofdm_rx_frames and ofdm_rx_density (who; profile: the record, or null; fr: the
-// frame record, or null; dn: the density record, or null -- without any, ofdm_rx, whose checks, arguments
-// and launch are then what they were)
-static int rx_call(const char* who, ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni,
-                   uint64_t seed, const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on,
-                   const uint8_t* bits, int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters,
-                   void* z_out, int64_t z_keep, int64_t* profile, const RxFrames* fr = nullptr,
-                   const RxDens* dn = nullptr) {
+// ofdm_rx, ofdm_rx_profile, ofdm_rx_frames and ofdm_rx_density (who): the receiver's arguments checked and
+// filled, then the entry point's own launch(a, r) -- the filled RxArgs, where the profile sets its record,
+// and the plan's precision as a value, float{} or double{} -- answered through checked() (layout_extra: its)
+// (extern "C++": a template inside this file's extern "C" block)
+extern "C++" template <typename L>
+static int rx_call(const char* who, ofdm_plan_t p, const void* y, const double* nr, const double* ni, uint64_t seed,
+                   const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on, const uint8_t* bits,
+                   int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters, void* z_out, int64_t z_keep,
+                   L launch, const std::string& layout_extra = {}) {
     RxArgs a{};
     bool run;
     const int rc = rx_args(who, p, y, nr, ni, seed, stats, total_samples, noise_on, bits, sym0, n_sym, n_valid_bits,
@@ -1005,42 +1005,17 @@ static int rx_call(const char* who, ofdm_plan_t p, void* stream, const void* y, 
     a.z_keep = z_out ? z_keep : 0;
     a.flags = OFDM_ENV_FLAGS("OFDM_ABLATE_RX");
     a.wide = p->wide_plan ? (const WideAxis*)p->wide.p : nullptr;  // an order above 256: the wide slicer
-    a.profile = profile;
-    if (fr) {
-        const RxFramesTail ft = frames_tail(*fr, sym0);
-        return checked(who, p, with_prec(p, [&](auto r) {
-            return launch_rx_frames<decltype(r)>(p->logn, a, ft, (hipStream_t)stream);
-        }));
-    }
-    if (dn) {
-        RxDensTail d{};  // (flush: the launcher's, by its workgroup shape)
-        d.hist = (unsigned long long*)dn->hist;
-        d.lo = dn->lo;
-        d.inv_w = dn->inv_w;
-        d.bins = dn->bins;
-        d.k_lo = dn->k_lo;
-        d.k_hi = dn->k_hi;
-        // (a generic-form layout that does not fit with the histogram: named, nothing was launched)
-        lds_extra = " with its " + std::to_string(dn->bins) + " x " + std::to_string(dn->bins) +
-                    " density histogram (" + std::to_string(4 * dn->bins * dn->bins) + " bytes)";
-        const int rc = checked(who, p, with_prec(p, [&](auto r) {
-            return launch_rx_dens<decltype(r)>(p->logn, a, d, (hipStream_t)stream);
-        }));
-        lds_extra.clear();
-        return rc;
-    }
-    return checked(who, p, with_prec(p, [&](auto r) {
-        using R = decltype(r);
-        return profile ? launch_rx_prof<R>(p->logn, a, (hipStream_t)stream) : launch_rx<R>(p->logn, a, (hipStream_t)stream);
-    }));
+    return checked(who, p, with_prec(p, [&](auto r) { return launch(a, r); }), layout_extra);
 }
 
 int ofdm_rx(ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni, uint64_t seed,
             const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on, const uint8_t* bits,
             int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters, void* z_out,
             int64_t z_keep) {
-    return rx_call("ofdm_rx", p, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0, n_sym,
-                   n_valid_bits, counters, z_out, z_keep, nullptr);
+    return rx_call("ofdm_rx", p, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0, n_sym, n_valid_bits,
+                   counters, z_out, z_keep, [&](RxArgs& a, auto r) {
+                       return launch_rx<decltype(r)>(p->logn, a, (hipStream_t)stream);
+                   });
 }
 
 int ofdm_rx_profile(ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni, uint64_t seed,
@@ -1048,8 +1023,11 @@ int ofdm_rx_profile(ofdm_plan_t p, void* stream, const void* y, const double* nr
                     const uint8_t* bits, int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters,
                     void* z_out, int64_t z_keep, int64_t* profile) {
     if (!profile) return fail(OFDM_E_INVALID, "ofdm_rx_profile needs a profile record");
-    return rx_call("ofdm_rx_profile", p, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0,
-                   n_sym, n_valid_bits, counters, z_out, z_keep, profile);
+    return rx_call("ofdm_rx_profile", p, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0, n_sym,
+                   n_valid_bits, counters, z_out, z_keep, [&](RxArgs& a, auto r) {
+                       a.profile = profile;
+                       return launch_rx_prof<decltype(r)>(p->logn, a, (hipStream_t)stream);
+                   });
 }
 
 int ofdm_rx_frames(ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni, uint64_t seed,
@@ -1058,8 +1036,10 @@ int ofdm_rx_frames(ofdm_plan_t p, void* stream, const void* y, const double* nr,
                    void* z_out, int64_t z_keep, int64_t frame_len, int64_t n_frames, uint64_t* frames) {
     const RxFrames fr{frame_len, n_frames, frames};
     if (const int rc = frames_ok("ofdm_rx_frames", fr, sym0, n_sym)) return rc;
-    return rx_call("ofdm_rx_frames", p, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0,
-                   n_sym, n_valid_bits, counters, z_out, z_keep, nullptr, &fr);
+    return rx_call("ofdm_rx_frames", p, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0, n_sym,
+                   n_valid_bits, counters, z_out, z_keep, [&](RxArgs& a, auto r) {
+                       return launch_rx_frames<decltype(r)>(p->logn, a, frames_tail(fr, sym0), (hipStream_t)stream);
+                   });
 }
 
 int ofdm_rx_density(ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni, uint64_t seed,
@@ -1069,8 +1049,20 @@ int ofdm_rx_density(ofdm_plan_t p, void* stream, const void* y, const double* nr
                     uint64_t* hist) {
     const RxDens dn{lo, inv_w, bins, k_lo, k_hi, hist};
     if (const int rc = dens_ok("ofdm_rx_density", dn, p ? p->n : 0)) return rc;
-    return rx_call("ofdm_rx_density", p, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0,
-                   n_sym, n_valid_bits, counters, z_out, z_keep, nullptr, nullptr, &dn);
+    RxDensTail d{};  // (flush: the launcher's, by its workgroup shape)
+    d.hist = (unsigned long long*)hist;
+    d.lo = lo;
+    d.inv_w = inv_w;
+    d.bins = bins;
+    d.k_lo = k_lo;
+    d.k_hi = k_hi;
+    // (a generic-form layout that does not fit with the histogram: named, nothing was launched)
+    return rx_call("ofdm_rx_density", p, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0, n_sym,
+                   n_valid_bits, counters, z_out, z_keep, [&](RxArgs& a, auto r) {
+                       return launch_rx_dens<decltype(r)>(p->logn, a, d, (hipStream_t)stream);
+                   },
+                   " with its " + std::to_string(bins) + " x " + std::to_string(bins) + " density histogram (" +
+                       std::to_string(4 * bins * bins) + " bytes)");
 }
 
 // ofdm_rx_sweep and ofdm_rx_sweep_frames (who; fr: the frame record of every point, or null -- without it

@@ -251,14 +251,32 @@ template <typename R, int FB, int LOGN>
 constexpr bool f64_rx_solo() {
     return sizeof(R) == 8 && ((FB > 1 && LOGN == 12) || (FB == 1 && LOGN == 11));
 }
+// The six receiver forms, named once, and each form's compile-time facts: what its kernel states in
+// __launch_bounds__ and in its `constexpr bool PROF, SWEEP, FRAMES, DENS` line, what the body
+// (ofdm_rx_body.hpp) sizes its workgroup and carves its LDS by, and what the launcher (rx_form_launch,
+// ofdm_kernels_inst.hpp) sizes, routes and launches by -- one description, so the three cannot disagree.
+enum class RxForm { Plain, Prof, Frames, Dens, Sweep, SweepFrames };
+template <RxForm F>
+struct RxFormOf {
+    static constexpr bool PROF = F == RxForm::Prof;                               // k_rx_prof
+    static constexpr bool SWEEP = F == RxForm::Sweep || F == RxForm::SweepFrames;    // k_rx_sweep, k_rx_sweep_frames
+    static constexpr bool FRAMES = F == RxForm::Frames || F == RxForm::SweepFrames;  // k_rx_frames, k_rx_sweep_frames
+    static constexpr bool DENS = F == RxForm::Dens;                               // k_rx_dens
+    // one wave per SIMD: the workgroup shape of rx_block / rx_waves / rx_carve (the reasons: rx_block)
+    static constexpr bool ONE_WAVE = PROF || SWEEP || DENS;
+};
 // MV: the complex128 SC-OFDM / zero-padding kernels (k_rx MV), ~10-50 VGPRs above their cyclic-prefix
 // OFDM twins: never the 4-wave shape, and the one-symbol N = 4096 shape at 2 waves per SIMD
-// PROF (k_rx_prof): a throughput receiver with the per-subcarrier profile keeps five accumulators per
-// element (~110 VGPRs) beside the kernel's own 130-200, so it runs at one wave per SIMD: 256 threads
-// (the one-symbol shapes as they are) instead of the 512 - 1024-thread shapes tuned to 128 - 168 registers
-template <typename R, int FB, int LOGN, int EQ, bool MV = false, bool PROF = false>
+// ONE_WAVE (RxFormOf, below): a throughput receiver with the per-subcarrier profile (k_rx_prof) keeps five
+// accumulators per element (~110 VGPRs) beside the kernel's own 130-200, so it runs at one wave per SIMD:
+// 256 threads (the one-symbol shapes as they are) instead of the 512 - 1024-thread shapes tuned to
+// 128 - 168 registers.  The sweep's throughput form (k_rx_sweep, k_rx_sweep_frames) takes the shape for the
+// y (64 VGPRs), the radii and the phase words it holds in registers across the points, and the density's
+// (k_rx_dens) because the throughput receivers fill the LDS at their own shapes (about 156 of 160 KB at
+// config b's) and this one leaves the histogram its 64 KB.
+template <typename R, int FB, int LOGN, int EQ, bool MV, bool ONE_WAVE>
 constexpr int rx_block() {
-    if (PROF && FB > 0) return f64_rx_solo<R, FB, LOGN>() ? (1 << LOGN) / 16 : 256;
+    if (ONE_WAVE && FB > 0) return f64_rx_solo<R, FB, LOGN>() ? (1 << LOGN) / 16 : 256;
     // (the adaptive kernel's per-order tables take ~200 VGPRs in complex128: 2 waves per SIMD)
     if (f64_rx_solo<R, FB, LOGN>()) return (1 << LOGN) / 16;  // one symbol
     if (sizeof(R) == 8 && FB > 0)
@@ -266,14 +284,14 @@ constexpr int rx_block() {
     if (FB > 0 && LOGN > 10) return OFDM_RX_BIG_BLOCK(LOGN);
     return FB > 1 && LOGN <= 10 && EQ == OFDM_EQ_NONE ? OFDM_RX_FAST_BLOCK : kBlock;
 }
-template <typename R, int FB, int LOGN, int EQ, bool MV = false, bool PROF = false>
+template <typename R, int FB, int LOGN, int EQ, bool MV, bool ONE_WAVE>
 constexpr int rx_waves() {
-    if (PROF && FB > 0) return 1;
+    if (ONE_WAVE && FB > 0) return 1;
     if (f64_rx_solo<R, FB, LOGN>()) return FB == 1 ? OFDM_F64_RX_ADAPT_WAVES : MV ? 2 : OFDM_F64_RX_SOLO_WAVES;
     if (sizeof(R) == 8 && FB > 0)
         return (LOGN > 10 || FB == 1) ? 2 : (f64_rx_wide<FB, LOGN, EQ, MV>() ? OFDM_F64_RX_WAVES : 3);
     if (FB > 0 && LOGN > 10) return OFDM_RX_BIG_WAVES;
-    return rx_block<R, FB, LOGN, EQ>() >= 512 ? 4 : OFDM_RX_WAVES;
+    return rx_block<R, FB, LOGN, EQ, MV, ONE_WAVE>() >= 512 ? 4 : OFDM_RX_WAVES;
 }
 // throughput RX: equaliser coefficients staged in LDS up to N = 2^OFDM_EQ_LDS_MAX_LOGN (beyond,
 // the table would cost a resident workgroup per CU)
@@ -1375,11 +1393,11 @@ struct RxLds {
 };
 // n_wide (generic kernel): the LUTs of a plan with an order above 256 (side 32 / 64 slicer tables)
 // n_sweep (k_rx_sweep): the SNR points of the launch (<= OFDM_MAX_SWEEP_POINTS), 0 in every other kernel
-// (PROF: the one-wave-per-SIMD workgroup shape, which k_rx_sweep's throughput form takes too)
-template <typename R, int LOGN, int EQ, int FB, bool MV, bool PROF = false, typename CV>
+// (ONE_WAVE: the form's workgroup shape, RxFormOf)
+template <typename R, int LOGN, int EQ, int FB, bool MV, bool ONE_WAVE, typename CV>
 __host__ __device__ __forceinline__ constexpr RxLds<R> rx_carve(CV& cv, int words_per_sym, int tts_all,
                                                                 int n_wide = 0, int n_sweep = 0) {
-    constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV, PROF>();
+    constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV, ONE_WAVE>();
     using G = Geo<LOGN, BLK>;
     using C = cpx<R>;
     constexpr bool SPLIT = split_rows<R, FB>();  // complex128 throughput: rows of reals
@@ -1464,19 +1482,23 @@ __device__ __forceinline__ void dens_bin(cpx<R> v, const RxDensTail& dt, uint32_
         ++outside;
 }
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
-__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB, LOGN, EQ, MV>())) void k_rx(
+__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::Plain>::ONE_WAVE>()),
+                             (rx_waves<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::Plain>::ONE_WAVE>())) void k_rx(
     RxArgs a) {
-    constexpr bool PROF = false, SWEEP = false, FRAMES = false, DENS = false;
+    using FORM = RxFormOf<RxForm::Plain>;
+    constexpr bool PROF = FORM::PROF, SWEEP = FORM::SWEEP, FRAMES = FORM::FRAMES, DENS = FORM::DENS;
 #include "ofdm_rx_body.hpp"
 }
 
 // The receiver that also accumulates the per-subcarrier profile: an instantiation of its own, so
 // that every k_rx compiles as before.  Instantiated for the generic kernel (and its WIDE form) and
-// for the complex128 cyclic-prefix OFDM throughput receivers of the bench shapes (ofdm_prof_inst.hpp).
+// for the complex128 cyclic-prefix OFDM throughput receivers of the bench shapes (ofdm_record_inst.hpp).
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
-__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<R, FB, LOGN, EQ, MV, true>())) void k_rx_prof(
+__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::Prof>::ONE_WAVE>()),
+                             (rx_waves<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::Prof>::ONE_WAVE>())) void k_rx_prof(
     RxArgs a) {
-    constexpr bool PROF = true, SWEEP = false, FRAMES = false, DENS = false;
+    using FORM = RxFormOf<RxForm::Prof>;
+    constexpr bool PROF = FORM::PROF, SWEEP = FORM::SWEEP, FRAMES = FORM::FRAMES, DENS = FORM::DENS;
 #include "ofdm_rx_body.hpp"
 }
 
@@ -1487,11 +1509,13 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<
 // k_rx's, so k_rx's own workgroup shapes and waves per SIMD.  The frame arguments are a second kernel
 // parameter (RxFramesTail) that only this kernel has: RxArgs and every other receiver stay what they
 // were.  Instantiated for the generic kernel (and its WIDE form) and for the complex128 cyclic-prefix
-// OFDM throughput receivers of the bench shapes (ofdm_frames_inst.hpp).
+// OFDM throughput receivers of the bench shapes (ofdm_record_inst.hpp).
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool WIDE = false>
-__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB, LOGN, EQ, MV>())) void k_rx_frames(
+__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::Frames>::ONE_WAVE>()),
+                             (rx_waves<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::Frames>::ONE_WAVE>())) void k_rx_frames(
     RxArgs a, RxFramesTail ft) {
-    constexpr bool PROF = false, SWEEP = false, FRAMES = true, DENS = false, REF = false;
+    using FORM = RxFormOf<RxForm::Frames>;
+    constexpr bool PROF = FORM::PROF, SWEEP = FORM::SWEEP, FRAMES = FORM::FRAMES, DENS = FORM::DENS, REF = false;
 #define OFDM_RX_BODY_FRAMES
 #include "ofdm_rx_body.hpp"
 #undef OFDM_RX_BODY_FRAMES
@@ -1505,17 +1529,19 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV>()), (rx_waves<R, FB,
 // record, and the workgroup's outside count one more.  Integers only: the record does not depend on the
 // grid, the batching or the rank count.  The throughput receivers fill the LDS at their own workgroup
 // shapes (about 156 of 160 KB at config b's), so the kernel takes the profile's one-wave-per-SIMD shape
-// (rx_block / rx_waves with PROF), which leaves the histogram its 64 KB.
+// (rx_block / rx_waves with ONE_WAVE), which leaves the histogram its 64 KB.
 // The 32-bit bins cannot wrap: one symbol-loop iteration bins at most SPB * N points, and after
 // RxDensTail::flush = floor((2^32 - 1) / (SPB * N)) iterations the workgroup adds its bins to the record
 // and zeroes them, a barrier on either side (a flush every >= 2^18 iterations: nothing beside a run's
 // other work).  The density arguments are a second kernel parameter (RxDensTail) that only this kernel
 // has.  Instantiated for the generic kernel (and its WIDE form) and for the complex128 cyclic-prefix OFDM
-// throughput receivers of the bench shapes (ofdm_dens_inst.hpp).
+// throughput receivers of the bench shapes (ofdm_record_inst.hpp).
 template <typename R, int LOGN, int EQ, int FB, bool MV, bool WIDE = false>
-__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<R, FB, LOGN, EQ, MV, true>())) void k_rx_dens(
+__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::Dens>::ONE_WAVE>()),
+                             (rx_waves<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::Dens>::ONE_WAVE>())) void k_rx_dens(
     RxArgs a, RxDensTail dt) {
-    constexpr bool PROF = false, SWEEP = false, FRAMES = false, DENS = true, REF = false;
+    using FORM = RxFormOf<RxForm::Dens>;
+    constexpr bool PROF = FORM::PROF, SWEEP = FORM::SWEEP, FRAMES = FORM::FRAMES, DENS = FORM::DENS, REF = false;
 #define OFDM_RX_BODY_DENS
 #include "ofdm_rx_body.hpp"
 #undef OFDM_RX_BODY_DENS
@@ -1528,11 +1554,13 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<
 // streams only.  Instantiated for the generic kernel (FB = 0: every plan that runs Philox streams) and
 // for the complex128 cyclic-prefix OFDM fixed-QAM bench shapes (ofdm_sweep_inst.hpp); the throughput
 // form keeps y (64 VGPRs), the radii and the phase words in registers across the points, so it takes
-// the profile's one-wave-per-SIMD workgroup shape (rx_block / rx_waves with PROF).
+// the profile's one-wave-per-SIMD workgroup shape (rx_block / rx_waves with ONE_WAVE).
 template <typename R, int LOGN, int EQ, int FB, bool MV>
-__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<R, FB, LOGN, EQ, MV, true>())) void k_rx_sweep(
+__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::Sweep>::ONE_WAVE>()),
+                             (rx_waves<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::Sweep>::ONE_WAVE>())) void k_rx_sweep(
     RxSweepArgs sa) {
-    constexpr bool PROF = false, SWEEP = true, FRAMES = false, DENS = false, REF = false, WIDE = false;
+    using FORM = RxFormOf<RxForm::Sweep>;
+    constexpr bool PROF = FORM::PROF, SWEEP = FORM::SWEEP, FRAMES = FORM::FRAMES, DENS = FORM::DENS, REF = false, WIDE = false;
     const RxArgs& a = sa.r;  // (a copy of its own that took each point's snr_lin in turn left the argument registers for memory)
 #define OFDM_RX_BODY_SWEEP
 #include "ofdm_rx_body.hpp"
@@ -1551,9 +1579,11 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<
 // arguments are the trailing kernel parameter (RxFramesTail, as k_rx_frames'): RxSweepArgs and every
 // other receiver stay what they were.  Instantiated as k_rx_sweep is (ofdm_sweep_inst.hpp: one routing).
 template <typename R, int LOGN, int EQ, int FB, bool MV>
-__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, true>()), (rx_waves<R, FB, LOGN, EQ, MV, true>())) void k_rx_sweep_frames(
+__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::SweepFrames>::ONE_WAVE>()),
+                             (rx_waves<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::SweepFrames>::ONE_WAVE>())) void k_rx_sweep_frames(
     RxSweepArgs sa, RxFramesTail ft) {
-    constexpr bool PROF = false, SWEEP = true, FRAMES = true, DENS = false, REF = false, WIDE = false;
+    using FORM = RxFormOf<RxForm::SweepFrames>;
+    constexpr bool PROF = FORM::PROF, SWEEP = FORM::SWEEP, FRAMES = FORM::FRAMES, DENS = FORM::DENS, REF = false, WIDE = false;
     const RxArgs& a = sa.r;  // (as k_rx_sweep)
 #define OFDM_RX_BODY_SWEEP
 #define OFDM_RX_BODY_FRAMES

@@ -255,7 +255,7 @@ static inline bool philox_streams(const RxArgs& a) {
 // (configs b, c: FB = 6), adaptive square-QAM loading at N = 2048 (config d: FB = 1), fixed 256-QAM at
 // N = 4096 (config e: FB = 8); 0 = no bench shape at this N and precision.  They are the shapes that have
 //   - REF instantiations of k_tx / k_rx (ref_shape: the caller's bits),
-//   - throughput forms of k_rx_prof (ofdm_prof_inst.hpp: Philox streams),
+//   - throughput forms of k_rx_prof, k_rx_frames and k_rx_dens (ofdm_record_inst.hpp: Philox streams),
 //   - throughput forms of k_rx_sweep (ofdm_sweep_inst.hpp: the fixed-QAM ones, FB > 1, only).
 template <typename R, int LOGN>
 constexpr int ref_fb() { return sizeof(R) == 8 ? (LOGN == 10 ? 6 : LOGN == 11 ? 1 : LOGN == 12 ? 8 : 0) : 0; }
@@ -332,18 +332,62 @@ static hipError_t rx_go(K fn, size_t sm, int rounds, int64_t n_sym, const A& a, 
     return hipGetLastError();
 }
 
-template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
-static hipError_t rx_launch(const RxArgs& a, hipStream_t s) {
-    constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV>();
-    if ((a.wide != nullptr) != WIDE) return hipErrorInvalidValue;  // (as tx_launch)
+// A form's kernel (RxForm, ofdm_fused.hpp) and the receiver's arguments inside the form's first kernel argument
+template <RxForm F, typename R, int LOGN, int EQ, int FB, bool MV, bool REF, bool WIDE>
+static auto rx_kernel() {
+    static_assert(F == RxForm::Plain || !REF, "the REF instantiations have no record and no sweep");
+    if constexpr (F == RxForm::Plain) return k_rx<R, LOGN, EQ, FB, MV, REF, WIDE>;
+    else if constexpr (F == RxForm::Prof) return k_rx_prof<R, LOGN, EQ, FB, MV, false, WIDE>;
+    else if constexpr (F == RxForm::Frames) return k_rx_frames<R, LOGN, EQ, FB, MV, WIDE>;
+    else if constexpr (F == RxForm::Dens) return k_rx_dens<R, LOGN, EQ, FB, MV, WIDE>;
+    else if constexpr (F == RxForm::Sweep) return k_rx_sweep<R, LOGN, EQ, FB, MV>;
+    else return k_rx_sweep_frames<R, LOGN, EQ, FB, MV>;
+}
+static inline const RxArgs& rx_of(const RxArgs& a) { return a; }
+static inline const RxArgs& rx_of(const RxSweepArgs& a) { return a.r; }
+static inline int rx_points(const RxArgs&) { return 0; }
+static inline int rx_points(const RxSweepArgs& a) { return a.n_snr; }
+
+// The one "size, fall back, go" of every receiver form (rx_launch, rx_record_launch, rx_sweep_launch): the
+// layout sized as the kernel carves it, by the form's own facts (RxFormOf: the workgroup shape; the sweep's
+// points inside rx_carve; the density's histogram behind the layout; the profile's LUT pool in static LDS);
+// a throughput layout that does not fit falls back to the generic kernel (EQ = -1, FB = 0, which builds
+// the modem variants in), and the generic kernel is the last resort: a shape it cannot hold is refused, not
+// launched (as tx_launch).  Then rx_go with the form's rounds.
+// a: RxArgs, or the sweeps' RxSweepArgs; tail: the kernel arguments behind it (RxFramesTail, RxDensTail)
+template <RxForm F, typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false, typename A,
+          typename... T>
+static hipError_t rx_form_launch(const A& a, hipStream_t s, T... tail) {
+    using FORM = RxFormOf<F>;
+    constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV, FORM::ONE_WAVE>();
+    using G = Geo<LOGN, BLK>;
+    const TxRxCommon& c = rx_of(a).c;
     CarveSize lds;
-    rx_carve<R, LOGN, EQ, FB, MV>(lds, a.c.words_per_sym, rx_tts<R, LOGN, FB>(a.c.scm), WIDE ? a.c.n_axis : 0);
-    if (lds.bytes + rx_static_lds<R, FB>() > kLdsPerCu) {  // (as tx_launch)
-        if constexpr (FB > 0) return rx_launch<R, LOGN, -1, 0, true>(a, s);
+    // (the profile's symbol slots reuse the FFT rows and the frame records need none: no dynamic LDS
+    // beyond the receiver's own)
+    rx_carve<R, LOGN, EQ, FB, MV, FORM::ONE_WAVE>(lds, c.words_per_sym, rx_tts<R, LOGN, FB>(c.scm), WIDE ? c.n_axis : 0,
+                                                  rx_points(a));
+    // the histogram behind the receiver's own layout, as the kernel carves it
+    if constexpr (FORM::DENS) (dens_lds(lds, tail.bins), ...);
+    constexpr size_t lut = FORM::PROF ? prof_lut_static<FB>() * sizeof(cpx<R>) : 0;
+    if (lds.bytes + rx_static_lds<R, FB>() + lut > kLdsPerCu) {
+        if constexpr (FB > 0) return rx_form_launch<F, R, LOGN, -1, 0, true>(a, s, tail...);
         else return kLdsOverflow;
     }
-    return rx_go<BLK, Geo<LOGN, BLK>::SPB>(k_rx<R, LOGN, EQ, FB, MV, REF, WIDE>, lds.bytes,
-                                           rx_grid_rounds<R, FB, LOGN>(), a.c.n_sym, a, s);
+    // one iteration of a workgroup bins at most SPB * N points (<= 16384): the 32-bit bins are flushed
+    // every `flush` iterations, before any of them could reach 2^32 (k_rx_dens) -- by the shape launched
+    if constexpr (FORM::DENS) ((tail.flush = (uint32_t)(0xFFFFFFFFull / ((unsigned long long)G::SPB * G::N))), ...);
+    // Two rounds of the resident workgroups where every workgroup ends with atomics of its own: up to five
+    // per subcarrier (profile), up to one per bin (density), a pair per point behind a table per point
+    // (the sweeps).  The frame record adds none per workgroup: k_rx's own grid.
+    constexpr int rounds = FORM::PROF || FORM::DENS || FORM::SWEEP ? 2 : rx_grid_rounds<R, FB, LOGN>();
+    return rx_go<BLK, G::SPB>(rx_kernel<F, R, LOGN, EQ, FB, MV, REF, WIDE>(), lds.bytes, rounds, c.n_sym, a, s, tail...);
+}
+
+template <typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false>
+static hipError_t rx_launch(const RxArgs& a, hipStream_t s) {
+    if ((a.wide != nullptr) != WIDE) return hipErrorInvalidValue;  // (as tx_launch)
+    return rx_form_launch<RxForm::Plain, R, LOGN, EQ, FB, MV, REF, WIDE>(a, s);
 }
 
 // MV: the run-time modem variants (SC-OFDM, zero padding) compiled in.  complex128 builds them as

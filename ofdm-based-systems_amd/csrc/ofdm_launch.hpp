@@ -317,15 +317,15 @@ template <typename R>
 hipError_t launch_tx(int logn, const TxArgs& a, int* grid, hipStream_t s);
 template <typename R>
 hipError_t launch_rx(int logn, const RxArgs& a, hipStream_t s);
-// the receiver with the per-subcarrier profile (a.profile set; ofdm_prof_inst.hpp)
+// the receiver with the per-subcarrier profile (a.profile set; ofdm_record_inst.hpp)
 template <typename R>
 hipError_t launch_rx_prof(int logn, const RxArgs& a, hipStream_t s);
 
-// the receiver with the per-frame error record (ofdm_frames_inst.hpp)
+// the receiver with the per-frame error record (ofdm_record_inst.hpp)
 template <typename R>
 hipError_t launch_rx_frames(int logn, const RxArgs& a, const RxFramesTail& f, hipStream_t s);
 
-// the receiver with the constellation-density record (ofdm_dens_inst.hpp)
+// the receiver with the constellation-density record (ofdm_record_inst.hpp)
 template <typename R>
 hipError_t launch_rx_dens(int logn, const RxArgs& a, const RxDensTail& d, hipStream_t s);
 

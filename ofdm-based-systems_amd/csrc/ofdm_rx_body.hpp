@@ -1,7 +1,7 @@
 // ofdm_rx_body.hpp -- the body of the fused receivers k_rx and k_rx_prof (ofdm_fused.hpp), included
 // into each kernel after its `constexpr bool PROF` (no include guard: included once per kernel).
 // In scope: the kernel's template parameters R, LOGN, EQ, FB, MV, REF, WIDE, its argument `RxArgs a`,
-// PROF, SWEEP, FRAMES and DENS.
+// the form's facts FORM (RxFormOf: its ONE_WAVE is the workgroup shape) and PROF, SWEEP, FRAMES and DENS.
 // DENS (k_rx_dens only, which defines OFDM_RX_BODY_DENS around its include and has its second argument
 // `RxDensTail dt` in scope): every equalised point is also binned into the density histogram in LDS.
 // FRAMES (k_rx_frames only, which defines OFDM_RX_BODY_FRAMES around its include and has its second
@@ -41,7 +41,7 @@
 #else
 #define OFDM_RX_SNR_LIN a.snr_lin
 #endif
-    constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV, PROF || SWEEP || DENS>();
+    constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV, FORM::ONE_WAVE>();
     using G = Geo<LOGN, BLK>;
     using C = cpx<R>;
     constexpr int N = G::N, E = G::E, TPS = G::TPS;
@@ -80,7 +80,7 @@
     constexpr int n_sweep = 0;
 #endif
     constexpr bool HOLD = SWEEP && F64_FAST;
-    const RxLds<R> lds = rx_carve<R, LOGN, EQ, FB, MV, PROF || SWEEP || DENS>(cv, cm.words_per_sym, tts_all, n_wide, n_sweep);
+    const RxLds<R> lds = rx_carve<R, LOGN, EQ, FB, MV, FORM::ONE_WAVE>(cv, cm.words_per_sym, tts_all, n_wide, n_sweep);
     C *tw = lds.tw, *tt = lds.tt, *eqt = lds.eqt;
     AxisInfo* axis = lds.axis;
     unsigned char* rowmem = lds.rowmem;

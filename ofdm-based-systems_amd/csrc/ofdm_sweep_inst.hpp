@@ -13,24 +13,12 @@ namespace ofdm {
 // adaptive loading re-derived per SNR is a different plan per point and not a sweep).
 // tail: nothing (k_rx_sweep), or the frame record's RxFramesTail (k_rx_sweep_frames,
 // ofdm_sweepframes_inst.hpp) -- one routing, one layout and one grid for both.
+// (the size, fall back, go: rx_form_launch)
 template <typename R, int LOGN, int EQ, int FB, typename... T>
 static hipError_t rx_sweep_launch(const RxSweepArgs& a, hipStream_t s, const T&... tail) {
     constexpr bool MV = FB == 0;  // (the generic kernel as rx_one launches it; compiled out of the fixed-QAM ones)
-    constexpr int BLK = rx_block<R, FB, LOGN, EQ, MV, true>();
-    const TxRxCommon& c = a.r.c;
-    CarveSize lds;
-    rx_carve<R, LOGN, EQ, FB, MV, true>(lds, c.words_per_sym, rx_tts<R, LOGN, FB>(c.scm), 0, a.n_snr);
-    if (lds.bytes + rx_static_lds<R, FB>() > kLdsPerCu) {
-        // (a layout that does not fit: the generic kernel, which is the last resort)
-        if constexpr (FB > 0) return rx_sweep_launch<R, LOGN, -1, 0>(a, s, tail...);
-        else return kLdsOverflow;
-    }
-    // Every workgroup builds a table per point and ends with an atomic pair per point: two rounds of
-    // the resident workgroups (as the profile's launcher)
-    if constexpr (sizeof...(T) == 0)
-        return rx_go<BLK, Geo<LOGN, BLK>::SPB>(k_rx_sweep<R, LOGN, EQ, FB, MV>, lds.bytes, 2, c.n_sym, a, s);
-    else
-        return rx_go<BLK, Geo<LOGN, BLK>::SPB>(k_rx_sweep_frames<R, LOGN, EQ, FB, MV>, lds.bytes, 2, c.n_sym, a, s, tail...);
+    constexpr RxForm F = sizeof...(T) == 0 ? RxForm::Sweep : RxForm::SweepFrames;
+    return rx_form_launch<F, R, LOGN, EQ, FB, MV>(a, s, tail...);
 }
 
 template <typename R, int LOGN, typename... T>

@@ -367,6 +367,56 @@ class _Share:
         return self.hi - self.lo
 
 
+@dataclass(frozen=True)
+class _Record:
+    """One record kind of the receiver, described once: the int64 words it takes in a run's buffer (_acc), what
+    it hands :meth:`LinkEngine.rx`, the receiver's event name with it, and how ``result()`` reads it."""
+    shape: tuple     # of the record; .words: their product
+    event: str
+    field: str       # of LinkStats
+    rx_kw: object    # the device record -> rx()'s keyword arguments
+    decode: object   # (the record on the host, int64; n_sym) -> the field's value
+    info: tuple = ()
+    words = property(lambda self: math.prod(self.shape))
+
+
+def _profile_record(n_fft: int, bits_per_subcarrier) -> _Record:
+    """ofdm_rx_profile's record, int64 [5][N] (the events keep ofdm_rx's name)."""
+    def decode(rec, n_sym):
+        rec = combine_profile([rec])
+        return SubcarrierProfile(bit_errors=rec[0], symbol_errors=rec[1], clipped=rec[4],
+                                 error_power=profile_power(rec), error_power_fx=rec[2:4].copy(),
+                                 n_symbols=n_sym, bits_per_subcarrier=bits_per_subcarrier)
+
+    return _Record((B.PROFILE_ROWS, n_fft), "ofdm_rx", "profile", lambda rec: {"profile": rec}, decode)
+
+
+def _frames_record(n_frames: int, frame_symbols: int, bps: int, n_valid: int, points: tuple = ()) -> _Record:
+    """ofdm_rx_frames' record, int64 [n_frames][2]; with ``points`` = (K,) ofdm_rx_sweep_frames' [K][n_frames][2],
+    which PendingSweep decodes point by point.  info: (F, bits per OFDM symbol, bits compared)."""
+    F = int(frame_symbols)
+
+    def decode(rec, n_sym):
+        rec = rec[:-(-n_sym // F)]  # (an empty run: no frame)
+        return FrameStats(frame_symbols=F, n_symbols=n_sym, bits_per_symbol=bps, bit_errors=rec[:, 0].copy(),
+                          symbol_errors=rec[:, 1].copy(), n_valid_bits=n_valid)
+
+    return _Record(points + (n_frames, 2), "ofdm_rx_sweep_frames" if points else "ofdm_rx_frames", "frames",
+                   lambda rec: {"frames": rec, "frame_symbols": F}, decode, (F, bps, n_valid))
+
+
+def _density_record(grid: tuple, subcarriers: tuple) -> _Record:
+    """ofdm_rx_density's record, int64 [G * G + 1]; grid: (lo, inv_w, G) of :func:`density_grid`."""
+    G, L = grid[2], -grid[0]
+
+    def decode(rec, n_sym):
+        return ConstellationDensity(counts=rec[:G * G].reshape(G, G).copy(), outside=int(rec[G * G]), extent=L,
+                                    n_points=int(rec.sum()), subcarriers=subcarriers)
+
+    return _Record((G * G + 1,), "ofdm_rx_density", "density",
+                   lambda rec: {"density": rec, "density_params": grid, "density_subcarriers": subcarriers}, decode)
+
+
 class LinkEngine:
     plan = None    # the libofdm_hip plan (set by __init__)
     _fused = None  # has_fused, asked of the library once per engine
@@ -574,12 +624,7 @@ class LinkEngine:
         edb = default_papr_edges_db() if edges_db is None else np.asarray(edges_db, dtype=np.float64).reshape(-1)
         edges = 10.0 ** (edb / 10.0)
         r = self._share(n_sym, group)
-        bits_d = None
-        if bits is not None:
-            need = math.ceil(n_sym * self.bps / 8)
-            if len(bits) < need:
-                raise ValueError(f"need {need} tx bytes for {n_sym} OFDM symbols, got {len(bits)}")
-            bits_d = self.upload(np.asarray(bits, dtype=np.uint8)[: math.ceil(r.hi * self.bps / 8) + 1])
+        bits_d = self._upload_bits(bits, n_sym, r)
         hist = torch.zeros(len(edges) + 1, dtype=torch.int64, device=r.dev)
         kept = max(0, min(int(keep), r.mine))
         sym_out = torch.zeros((kept, 2), dtype=torch.float64, device=r.dev) if kept else None
@@ -593,9 +638,7 @@ class LinkEngine:
         if r.mine == 0:  # (an empty shard still answers for the arguments)
             self.papr_hist(r.stream, bits_d, seed, r.lo, 0, edges, hist, None, 0)
         done, work = self._finish(hist, group, r.dev)
-        pend = _Pending()
-        pend.done, pend.work, pend.counters = done, work, hist
-        pend._wait()
+        _Pending(n_sym, 0, None, hist, done, work)._wait()
         return PaprStats(edges_db=edb.copy(), histogram=hist.cpu().numpy().astype(np.int64),
                          num_ofdm_symbols=int(n_sym),
                          per_symbol=None if sym_out is None else sym_out.cpu().numpy(),
@@ -652,6 +695,24 @@ class LinkEngine:
         lo, hi = shard(n_sym, rank, world)
         n_valid = self.valid_bits(n_sym) if n_valid_bits is None else int(n_valid_bits)
         return _Share(self.device(), self.stream(), world, lo, hi, n_sym * (self.n_fft + self.cp), n_valid)
+
+    def _upload_bits(self, bits, n_sym: int, r: _Share):
+        """The caller's packed tx bytes on the device, up to this rank's last symbol (None: Philox bits)."""
+        if bits is None:
+            return None
+        need = math.ceil(n_sym * self.bps / 8)
+        if len(bits) < need:
+            raise ValueError(f"need {need} tx bytes for {n_sym} OFDM symbols, got {len(bits)}")
+        return self.upload(np.asarray(bits, dtype=np.uint8)[: math.ceil(r.hi * self.bps / 8) + 1])
+
+    def _acc(self, n_counters: int, rec: Optional[_Record], dev) -> tuple:
+        """A run's one int64 buffer, which one all-reduce carries: the counters, and behind them the clip
+        record (an engine with a clip level: [2]) and the record ``rec`` describes (profile, frames or density;
+        every rank adds its own symbols' counts into the whole run's).  (buffer, counters, clip, record)."""
+        nclip = 0 if self.clip_a2 is None else 2
+        acc = torch.zeros(n_counters + nclip + (rec.words if rec else 0), dtype=torch.int64, device=dev)
+        return (acc, acc[:n_counters], acc[n_counters:n_counters + nclip] if nclip else None,
+                acc[n_counters + nclip:].view(rec.shape) if rec else None)
 
     def _y(self, n_sym: int) -> torch.Tensor:
         """The kept channel samples of n_sym OFDM symbols."""
@@ -799,7 +860,7 @@ class LinkEngine:
                 raise ValueError("profile=True together with frame_symbols: the receiver with both records "
                                  "(PROF x FRAMES) is not built; run twice")
             n_frames = frame_count(n_sym, frame_symbols)
-        n_dens, dgrid, drange = 0, None, None
+        dgrid = None
         if density is not None:
             if profile:
                 raise ValueError("profile=True together with density: the receiver with both records "
@@ -813,52 +874,35 @@ class LinkEngine:
             if len(drange) != 2 or not 0 <= drange[0] < drange[1] <= self.n_fft:
                 raise ValueError(f"density_subcarriers = {density_subcarriers!r} is not a range "
                                  f"0 <= k_lo < k_hi <= {self.n_fft}")
-            n_dens = int(density) ** 2 + 1
         elif density_extent is not None or density_subcarriers is not None:
             raise ValueError("density_extent / density_subcarriers without density")
         r = self._share(n_sym, group, n_valid_bits)
         dev, N = r.dev, self.n_fft
+        # the run's record, at most one (the pairs were refused above)
+        rec = (_profile_record(N, self.bits_per_subcarrier) if profile else
+               _frames_record(n_frames, frame_symbols, self.bps, r.n_valid) if n_frames else
+               _density_record(dgrid, drange) if dgrid else None)
         use_link = self._route_fused(fused, philox=bits is None and normals is None, tap=keep_symbols > 0,
-                                     profile=profile or n_frames > 0 or n_dens > 0,
-                                     whole=r.n_valid >= n_sym * self.bps)
+                                     profile=rec is not None, whole=r.n_valid >= n_sym * self.bps)
 
-        bits_d = None
-        if bits is not None:
-            need = math.ceil(n_sym * self.bps / 8)
-            if len(bits) < need:
-                raise ValueError(f"need {need} tx bytes for {n_sym} OFDM symbols, got {len(bits)}")
-            bits_d = self.upload(np.asarray(bits, dtype=np.uint8)[: math.ceil(r.hi * self.bps / 8) + 1])
+        bits_d = self._upload_bits(bits, n_sym, r)
         nr_d = ni_d = None
         if normals is not None and noise_on:
             nr_d = self.upload(np.asarray(normals[0], np.float64))
             ni_d = self.upload(np.asarray(normals[1], np.float64))
 
         stats = new_stats(dev)
-        # the counters, and behind them the clip record and the profile, frame or density record: one
-        # buffer, one all-reduce (every rank adds its own symbols' counts into the whole run's frame or
-        # density record)
-        nclip = 0 if self.clip_a2 is None else 2
-        acc = torch.zeros(2 + nclip + (B.PROFILE_ROWS * N if profile else 0) + 2 * n_frames + n_dens,
-                          dtype=torch.int64, device=dev)
-        counters = acc[:2]
-        clip = acc[2:4] if nclip else None
-        prof = acc[2 + nclip:].view(B.PROFILE_ROWS, N) if profile else None
-        pkw = {"profile": prof} if profile else {}  # (rx without a profile is called as before)
-        frec = acc[2 + nclip:].view(n_frames, 2) if n_frames else None
-        if n_frames:  # (and without a frame record)
-            pkw = {"frames": frec, "frame_symbols": int(frame_symbols)}
-        drec = acc[2 + nclip:] if n_dens else None
-        if n_dens:  # (and without a density record)
-            pkw = {"density": drec, "density_params": dgrid, "density_subcarriers": drange}
+        acc, counters, clip, record = self._acc(2, rec, dev)
+        pkw = rec.rx_kw(record) if rec else {}  # (rx without a record is called as before)
         keep = min(keep_symbols, r.mine)
         z_out = torch.empty((keep, N), dtype=self.cdtype, device=dev) if keep else None
-        rx_name = "ofdm_rx_density" if n_dens else "ofdm_rx_frames" if n_frames else "ofdm_rx"
+        rx_name = rec.event if rec else "ofdm_rx"
 
         def receive(y, sym0, n, resident):
             zk = keep if sym0 == r.lo else 0  # the tap: the shard's first symbols, so its first batch
             # (a density record: the later batches of a run with a tap keep the tap buffer, z_keep = 0, so
             # that every batch takes the generic receiver -- one form per run, ofdm_rx_density)
-            zo = z_out if zk or n_dens else None
+            zo = z_out if zk or dgrid else None
             self._timed(events if resident else None, rx_name, n, lambda: self.rx(
                 r.stream, y, nr_d, ni_d, seed, stats, r.samples, snr_db, noise_on, bits_d, sym0, n, r.n_valid,
                 counters, zo, zk, **pkw))
@@ -869,10 +913,7 @@ class LinkEngine:
 
         done, work = self._schedule(r, seed, bits_d, stats, receive, acc, group=group, y_budget=y_budget,
                                     batch=batch, events=events, link=link if use_link else None, clip=clip)
-        return PendingLink(n_sym, r.samples, stats, counters, z_out, done, work, prof,
-                           self.bits_per_subcarrier if profile else None, clip=clip, clip_db=self.clip_db,
-                           frames=frec, frame_info=(int(frame_symbols), self.bps, r.n_valid) if n_frames else None,
-                           density=drec, density_info=(dgrid[2], -dgrid[0], drange) if n_dens else None)
+        return PendingLink(n_sym, r.samples, stats, counters, done, work, clip, self.clip_db, record, rec, z_out)
 
     # ------------------------------------------------------------------ one-pass SNR sweep
     def run_sweep(self, n_sym: int, snr_dbs, **kw) -> list:
@@ -950,27 +991,21 @@ class LinkEngine:
                              "record); use longer frames, shorter runs or fewer points per sweep")
         r = self._share(n_sym, group, n_valid_bits)
         stats = new_stats(r.dev)
-        # the [K][2] counters, and behind them the clip record and the [K][n_frames][2] frame record: one
-        # buffer, one all-reduce (every rank adds its own symbols' counts into the whole run's record)
-        nclip = 0 if self.clip_a2 is None else 2
-        acc = torch.zeros(2 * K + nclip + 2 * K * n_frames, dtype=torch.int64, device=r.dev)
-        counters = acc[:2 * K].view(K, 2)
-        clip = acc[2 * K:2 * K + nclip] if nclip else None
-        frec = acc[2 * K + nclip:].view(K, n_frames, 2) if n_frames else None
-        rx_name = "ofdm_rx_sweep_frames" if n_frames else "ofdm_rx_sweep"
+        rec = _frames_record(n_frames, frame_symbols, self.bps, r.n_valid, (K,)) if n_frames else None
+        acc, counters, clip, frec = self._acc(2 * K, rec, r.dev)  # (the [K][2] counters, the [K][n_frames][2] record)
+        counters = counters.view(K, 2)
+        rx_name = rec.event if rec else "ofdm_rx_sweep"
 
         def receive(y, sym0, n, resident):  # (timed per launch on either path)
             for k0 in range(0, K, B.MAX_SWEEP_POINTS):
                 k1 = k0 + B.MAX_SWEEP_POINTS
-                # (rx_sweep without a frame record is called as before)
-                fkw = {"frames": frec[k0:k1], "frame_symbols": int(frame_symbols)} if n_frames else {}
+                fkw = rec.rx_kw(frec[k0:k1]) if rec else {}  # (rx_sweep without a frame record is called as before)
                 self._timed(events, rx_name, n, lambda: self.rx_sweep(
                     r.stream, y, seed, stats, r.samples, snrs[k0:k1], sym0, n, r.n_valid, counters[k0:k1], **fkw))
 
         done, work = self._schedule(r, seed, None, stats, receive, acc, group=group, y_budget=y_budget,
                                     batch=batch, events=events, clip=clip)
-        return PendingSweep(n_sym, r.samples, stats, counters, done, work, clip=clip, clip_db=self.clip_db,
-                            frames=frec, frame_info=(int(frame_symbols), self.bps, r.n_valid) if n_frames else None)
+        return PendingSweep(n_sym, r.samples, stats, counters, done, work, clip, self.clip_db, frec, rec)
 
     def lane_streams(self, lanes: int) -> list:
         """The current stream and lanes - 1 more, kept per engine (their allocator pools persist:
@@ -1068,7 +1103,7 @@ class LinkEngine:
                 self._timed(events, "ofdm_rx", mine, lambda: self.rx(
                     stream, y, None, None, seed, stats, r.samples, snr, True, None, lo, mine, r.n_valid, counters))
             done, red = self._finish(counters, group, dev)
-            return PendingLink(n_sym, r.samples, stats, counters, None, done, red)
+            return PendingLink(n_sym, r.samples, stats, counters, done, red)
 
         out = []
         cur = tx(0) if seeds else None
@@ -1080,8 +1115,15 @@ class LinkEngine:
 
 
 class _Pending:
-    """Device-side results of a run: its statistics record and counters, the ``done`` event of its
-    launch stream and ``work``, its asynchronous counter all-reduce (multi-rank) or None."""
+    """Device-side results of a run: its statistics record and counters (of papr(): its histogram), the ``done``
+    event of its launch stream and ``work``, its asynchronous counter all-reduce (multi-rank) or None; its clip
+    record (a clip level: device int64 [2]); its record and the record's description (_Record); run_async's tap."""
+
+    def __init__(self, n_sym, samples, stats, counters, done=None, work=None, clip=None, clip_db=None,
+                 record=None, kind=None, z_out=None):
+        self.n_sym, self.samples, self.stats, self.counters = n_sym, samples, stats, counters
+        self.done, self.work, self.clip, self.clip_db = done, work, clip, clip_db
+        self.record, self.kind, self.z_out = record, kind, z_out
 
     def _wait(self) -> None:
         if self.done is not None:
@@ -1091,9 +1133,6 @@ class _Pending:
             self.work = None
             if self.counters.is_cuda:
                 torch.cuda.current_stream().synchronize()
-
-    clip = None     # the run's clip record (device int64 [2]) on an engine with a clip level
-    clip_db = None
 
     def _statistics(self) -> dict:
         """LinkStats' fields from the run's statistics record (the same for every SNR point of a sweep),
@@ -1112,46 +1151,14 @@ class _Pending:
 class PendingLink(_Pending):
     """Device-side results of one :meth:`LinkEngine.run_async` call."""
 
-    def __init__(self, n_sym, samples, stats, counters, z_out, done=None, work=None, profile=None,
-                 bits_per_subcarrier=None, clip=None, clip_db=None, frames=None, frame_info=None,
-                 density=None, density_info=None):
-        self.n_sym, self.samples = n_sym, samples
-        self.clip, self.clip_db = clip, clip_db
-        # the run's frame record (device int64 [n_frames][2]) and (F, bits per OFDM symbol, bits compared)
-        self.frames, self.frame_info = frames, frame_info
-        # the run's density record (device int64 [G * G + 1]) and (G, L, (k_lo, k_hi))
-        self.density, self.density_info = density, density_info
-        self.stats, self.counters, self.z_out = stats, counters, z_out
-        self.profile, self.bits_per_subcarrier = profile, bits_per_subcarrier
-        self.done, self.work = done, work
-
     def result(self) -> LinkStats:
         self._wait()
         shared = self._statistics()
         cnt = self.counters.cpu().numpy()
-        z = self.z_out
-        prof = None
-        if self.profile is not None:
-            rec = combine_profile([self.profile.cpu().numpy()])
-            prof = SubcarrierProfile(bit_errors=rec[0], symbol_errors=rec[1], clipped=rec[4],
-                                     error_power=profile_power(rec), error_power_fx=rec[2:4].copy(),
-                                     n_symbols=self.n_sym,
-                                     bits_per_subcarrier=self.bits_per_subcarrier)
-        fr = None
-        if self.frames is not None:
-            F, bps, n_valid = self.frame_info
-            rec = self.frames.cpu().numpy().astype(np.int64)[:-(-self.n_sym // F)]  # (an empty run: no frame)
-            fr = FrameStats(frame_symbols=F, n_symbols=self.n_sym, bits_per_symbol=bps, bit_errors=rec[:, 0].copy(),
-                            symbol_errors=rec[:, 1].copy(), n_valid_bits=n_valid)
-        dens = None
-        if self.density is not None:
-            G, L, rng = self.density_info
-            rec = self.density.cpu().numpy().astype(np.int64)
-            dens = ConstellationDensity(counts=rec[:G * G].reshape(G, G).copy(), outside=int(rec[G * G]), extent=L,
-                                        n_points=int(rec.sum()), subcarriers=rng)
-        return LinkStats(bit_errors=int(cnt[0]), symbol_errors=int(cnt[1]),
-                         received=None if z is None else z.cpu().numpy().reshape(-1), profile=prof, frames=fr,
-                         density=dens, **shared)
+        if self.kind is not None:
+            shared[self.kind.field] = self.kind.decode(self.record.cpu().numpy().astype(np.int64), self.n_sym)
+        return LinkStats(bit_errors=int(cnt[0]), symbol_errors=int(cnt[1]), **shared,
+                         received=None if self.z_out is None else self.z_out.cpu().numpy().reshape(-1))
 
 
 class PendingSweep(_Pending):
@@ -1159,14 +1166,10 @@ class PendingSweep(_Pending):
     the run's one statistics record; of :meth:`LinkEngine.run_frame_sweep_async` also the
     [K][n_frames][2] frame record."""
 
-    def __init__(self, n_sym, samples, stats, counters, done=None, work=None, clip=None, clip_db=None,
-                 frames=None, frame_info=None):
-        self.n_sym, self.samples = n_sym, samples
-        self.clip, self.clip_db = clip, clip_db
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
         # the points' frame records (device int64 [K][n_frames][2]) and (F, bits per OFDM symbol, bits compared)
-        self.frames, self.frame_info = frames, frame_info
-        self.stats, self.counters = stats, counters
-        self.done, self.work = done, work
+        self.frames, self.frame_info = self.record, self.kind.info if self.kind else None
 
     def result(self) -> list:
         """One LinkStats per SNR point, in the order given: the point's counts and the run's shared
@@ -1176,10 +1179,6 @@ class PendingSweep(_Pending):
         cnt = self.counters.cpu().numpy()
         if self.frames is None:
             return [LinkStats(bit_errors=int(c[0]), symbol_errors=int(c[1]), **shared) for c in cnt]
-        F, bps, n_valid = self.frame_info
-        rec = self.frames.cpu().numpy().astype(np.int64)[:, :-(-self.n_sym // F)]  # (as PendingLink.result)
-        return [LinkStats(bit_errors=int(c[0]), symbol_errors=int(c[1]),
-                          frames=FrameStats(frame_symbols=F, n_symbols=self.n_sym, bits_per_symbol=bps,
-                                            bit_errors=p[:, 0].copy(), symbol_errors=p[:, 1].copy(),
-                                            n_valid_bits=n_valid), **shared)
+        rec = self.frames.cpu().numpy().astype(np.int64)
+        return [LinkStats(bit_errors=int(c[0]), symbol_errors=int(c[1]), frames=self.kind.decode(p, self.n_sym), **shared)
                 for c, p in zip(cnt, rec)]

@@ -121,7 +121,7 @@ def test_ab_only_variant_reports_kernels_it_lacks():
     assert "kAbOnly = false" in branch(launch, "constexpr bool kAbOnly", False)
 
     # the translation sits in checked(), guarded by kAbOnly, and nowhere else (HIPCHK serves HIP calls)
-    checked = abi[abi.index("int checked(const char* who, ofdm_plan_t p, hipError_t e) {"):]
+    checked = abi[abi.index("int checked(const char* who, ofdm_plan_t p, hipError_t e, const std::string& layout_extra = {}) {"):]
     checked = checked[:checked.index("\n}\n")]
     m = re.search(r"if \(kAbOnly && e == kNotInBuild\)\s*return fail\(OFDM_E_INVALID,(.*?)\);", checked, flags=re.S)
     assert m and "kernel not in this build" in m.group(1), checked

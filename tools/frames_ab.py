@@ -47,7 +47,7 @@ def static_counts(hipcc="/opt/rocm/bin/hipcc"):
     loop, the branch a symbol with errors takes included -- and the receiver loop they are set against is
     k_rx's largest loop (the symbol loop; where the layout folds the short reduction loops behind it into
     the same back edge it is a few per cent larger, which makes the estimate smaller by as much)."""
-    src = '#include "ofdm_frames_inst.hpp"\nnamespace ofdm {\n' + "".join(
+    src = '#include "ofdm_record_inst.hpp"\nnamespace ofdm {\n' + "".join(
         f"template __global__ void k_rx<{a}, false, false>(RxArgs);\n"
         f"template __global__ void k_rx_frames<{a}, false>(RxArgs, RxFramesTail);\n" for a in STATIC.values()) + "}\n"
     out = {}

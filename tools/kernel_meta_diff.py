@@ -80,7 +80,10 @@ def texts(path):
         for part in re.split(r"\n(?=[0-9a-f]{8,} <)", dis):
             head = re.match(r"[0-9a-f]+ <(\S+)>:\n", part)
             if head:
-                out[head.group(1)] = re.sub(r"// [0-9A-F]+:", "//", part[head.end():])
+                # (a trailing "..." is the zero fill up to the next symbol's alignment: it belongs to the
+                # order of the kernels in the object, not to the kernel)
+                body = re.sub(r"\n\s*\.\.\.\s*$", "\n", part[head.end():].rstrip() + "\n")
+                out[head.group(1)] = re.sub(r"// [0-9A-F]+:", "//", body)
     names = list(out)
     dem = subprocess.run(["c++filt"], input="\n".join(names), check=True,
                          capture_output=True, text=True).stdout.split("\n")
@@ -109,15 +112,16 @@ def main():
     ap.add_argument("this")
     a = ap.parse_args()
     old, new = kernels(a.parent), kernels(a.this)
-    fused = [k for k in old if k.startswith(("k_tx<", "k_rx<", "k_rx_prof<"))]
+    families = ("k_tx", "k_rx", "k_rx_prof", "k_rx_frames", "k_rx_dens", "k_rx_sweep", "k_rx_sweep_frames")
+    fused = [k for k in old if k.startswith(tuple(f + "<" for f in families))]
     other = [k for k in old if k not in fused]
     diff_f = [k for k in fused if new.get(k) != old[k]]
     diff_o = [k for k in other if new.get(k) != old[k]]
     print("# Kernel metadata of libofdm_hip.so (llvm-readelf --notes on its gfx950 code objects), parent commit "
           "against this\n# commit: " + ", ".join(FIELDS) + " per kernel.")
-    n = lambda p: sum(k.startswith(p) for k in fused)
-    print(f"# fused kernels of the parent build: {len(fused)} (k_tx {n('k_tx<')}, k_rx {n('k_rx<')}, k_rx_prof "
-          f"{n('k_rx_prof<')}); with different figures in this build: {len(diff_f)}")
+    counts = ", ".join(f"{f} {sum(k.startswith(f + '<') for k in fused)}" for f in families)
+    print(f"# fused kernels of the parent build: {len(fused)} ({counts}); with different figures in this build: "
+          f"{len(diff_f)}")
     print(f"# other kernels of the parent build: {len(other)}, different: {len(diff_o)}")
     for k in diff_f + diff_o:
         print("# DIFFERENT:", k, old[k], "->", new.get(k))
