@@ -40,8 +40,8 @@ extern "C" {
 #define OFDM_MAX_SWEEP_POINTS 40
 
 /* The supported symbol range: every entry point that takes sym0 and n_sym (ofdm_tx, ofdm_tx_clip,
- * ofdm_rx, ofdm_rx_profile, ofdm_rx_frames, ofdm_rx_density, ofdm_rx_sweep, the four ofdm_link* and
- * ofdm_papr) returns OFDM_E_INVALID, before any launch, when sym0 + n_sym > OFDM_MAX_SYMBOLS.
+ * ofdm_rx, ofdm_rx_profile, ofdm_rx_frames, ofdm_rx_density, ofdm_rx_sweep, the four ofdm_link*,
+ * ofdm_papr and ofdm_hip_soft.h's receiver) returns OFDM_E_INVALID, before any launch, when sym0 + n_sym > OFDM_MAX_SYMBOLS.
  * The host and the kernels form global bit positions s * bps + offset in int64_t (the n_valid_bits
  * mask, the caller's bits and their byte count), s < sym0 + n_sym and bps the bits per OFDM symbol.
  * The largest plan has 4096 subcarriers of 12 bits (4096-QAM): bps <= 49152 < 2^16, and an offset
@@ -383,6 +383,10 @@ int ofdm_rx_density(ofdm_plan_t plan, void* stream, const void* y, const double*
                     int32_t noise_on, const uint8_t* bits, int64_t sym0, int64_t n_sym,
                     int64_t n_valid_bits, uint64_t* counters, void* z_out, int64_t z_keep,
                     double lo, double inv_w, int32_t bins, int32_t k_lo, int32_t k_hi, uint64_t* hist);
+
+/* The receiver with a soft-decision record of the run, ofdm_rx_soft -- for every compared bit the max-log
+ * distance difference, binned into a histogram conditioned on the transmitted bit -- is declared in the
+ * extension header ofdm_hip_soft.h (an entry point added to ABI 6 in the same library; nothing here changes). */
 
 /*
  * The one-pass SNR sweep receiver (an entry point added to ABI 6: nothing of the version's existing

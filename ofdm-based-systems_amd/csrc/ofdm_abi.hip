@@ -1,4 +1,4 @@
-// ofdm_abi.hip -- C ABI of libofdm_hip.so (include/ofdm_hip.h, ofdm_hip_sweep_frames.h): plan management,
+// ofdm_abi.hip -- C ABI of libofdm_hip.so (include/ofdm_hip.h, ofdm_hip_sweep_frames.h, ofdm_hip_soft.h): plan management,
 // argument validation, error reporting, and dispatch to the gfx950 kernels.
 //
 // A plan owns only constant tables (twiddles, LUTs, normalised CIR, equaliser
@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ofdm_hip.h"
+#include "ofdm_hip_soft.h"
 #include "ofdm_hip_sweep_frames.h"
 #include "ofdm_launch.hpp"
 
@@ -118,6 +119,9 @@ struct ofdm_plan_s {
     // LUT has more than 256 entries, so the fused kernels stage no LUT and use the WideAxis table
     DevBuf wide;
     int max_bits, wide_plan;
+    // ofdm_rx_soft's level table, double[n_luts][2][kSoftSide]: per LUT of side <= 16 the I levels
+    // LUT[a].re and the Q levels LUT[a << hb].im by index bits a, the LUT's own doubles (zeros otherwise)
+    DevBuf softlev;
     // an MMSE plan whose response is exactly zero on some subcarrier: its equalised symbol there is an
     // exact zero in every OFDM symbol, the tie AxisInfo::zero_i / zero_q decide -- every receiver
     // launch of the plan takes the generic kernel, which applies them (RxArgs::zero_tie)
@@ -421,6 +425,18 @@ int ofdm_plan_create(ofdm_plan_t* out, const ofdm_desc* d, void* stream) {
         if ((rc = upload(p->lut64, pool.data(), pool.size(), s))) return rc;
         if ((rc = upload(p->axis, axes.data(), axes.size(), s))) return rc;
         if ((rc = upload(p->wide, wides.data(), wides.size(), s))) return rc;
+        {
+            std::vector<double> sl((size_t)d->n_luts * 2 * kSoftSide, 0.0);
+            for (int i = 0; i < d->n_luts; ++i) {
+                const AxisInfo& ax = axes[i];
+                if (ax.side < 2 || ax.side > kSoftSide) continue;
+                for (int a = 0; a < ax.side; ++a) {
+                    sl[((size_t)i * 2 + 0) * kSoftSide + a] = d->lut_pool[2 * (ax.lut_off + a)];
+                    sl[((size_t)i * 2 + 1) * kSoftSide + a] = d->lut_pool[2 * (ax.lut_off + (a << ax.hbits)) + 1];
+                }
+            }
+            if ((rc = upload(p->softlev, sl.data(), sl.size(), s))) return rc;
+        }
         p->max_bits = 0;
         if (p->adaptive) {
             std::vector<ScInfo> sc(p->n);
@@ -986,7 +1002,36 @@ static int dens_ok(const char* who, const RxDens& d, int n_fft) {
                   ") is not 0 <= k_lo < k_hi <= n_fft" + (n_fft > 0 ? " = " + std::to_string(n_fft) : std::string()));
     return (int)OFDM_OK;
 }
-// ofdm_rx, ofdm_rx_profile, ofdm_rx_frames and ofdm_rx_density (who): the receiver's arguments checked and
+// ofdm_rx_soft's record, scale table and grid (ofdm_hip_soft.h)
+struct RxSoft {
+    const double* g;
+    double inv_w;
+    int32_t bins, k_lo, k_hi;
+    uint64_t* hist;
+};
+// The soft record's own refusals, made before anything else is looked at (p: the plan or null, which
+// rx_args then refuses): the arguments, then what of the plan's constellations has no soft form
+static int soft_ok(const char* who, const RxSoft& d, ofdm_plan_t p) {
+    const auto no = [&](const std::string& why) { return fail(OFDM_E_INVALID, std::string(who) + ": " + why); };
+    const int n_fft = p ? p->n : 0;
+    if (!d.hist) return no("needs a soft-decision record");
+    if (!d.g) return no("needs the subcarriers' scale table g");
+    if (d.bins < 2 || d.bins > OFDM_MAX_SOFT_BINS || (d.bins & 1))
+        return no("bins " + std::to_string(d.bins) + " is not an even number in [2, " + std::to_string(OFDM_MAX_SOFT_BINS) + "]");
+    if (!std::isfinite(d.inv_w) || !(d.inv_w > 0)) return no("inv_w is not a finite positive bin rate");
+    if (d.k_lo < 0 || d.k_lo >= d.k_hi || (n_fft > 0 && d.k_hi > n_fft))
+        return no("the subcarrier range [" + std::to_string(d.k_lo) + ", " + std::to_string(d.k_hi) +
+                  ") is not 0 <= k_lo < k_hi <= n_fft" + (n_fft > 0 ? " = " + std::to_string(n_fft) : std::string()));
+    if (p && p->has_const) {
+        if (p->wide_plan)
+            return no("the plan has a constellation above 256 points, and the soft record of such an order is not built");
+        if (!p->separable)
+            return no("the plan has a non-separable (PSK) constellation, and the soft record of one is not built "
+                      "(square QAM of order 4, 16, 64 or 256 only)");
+    }
+    return (int)OFDM_OK;
+}
+// ofdm_rx, ofdm_rx_profile, ofdm_rx_frames, ofdm_rx_density and ofdm_rx_soft (who): the receiver's arguments checked and
 // filled, then the entry point's own launch(a, r) -- the filled RxArgs, where the profile sets its record,
 // and the plan's precision as a value, float{} or double{} -- answered through checked() (layout_extra: its)
 // (extern "C++": a template inside this file's extern "C" block)
@@ -1063,6 +1108,29 @@ int ofdm_rx_density(ofdm_plan_t p, void* stream, const void* y, const double* nr
                    },
                    " with its " + std::to_string(bins) + " x " + std::to_string(bins) + " density histogram (" +
                        std::to_string(4 * bins * bins) + " bytes)");
+}
+
+int ofdm_rx_soft(ofdm_plan_t p, void* stream, const void* y, const double* nr, const double* ni, uint64_t seed,
+                 const ofdm_stats* stats, int64_t total_samples, double snr_db, int32_t noise_on, const uint8_t* bits,
+                 int64_t sym0, int64_t n_sym, int64_t n_valid_bits, uint64_t* counters, void* z_out, int64_t z_keep,
+                 const double* g, double inv_w, int32_t bins, int32_t k_lo, int32_t k_hi, uint64_t* hist) {
+    const RxSoft sd{g, inv_w, bins, k_lo, k_hi, hist};
+    if (const int rc = soft_ok("ofdm_rx_soft", sd, p)) return rc;
+    RxSoftTail t{};  // (flush: the launcher's, by its workgroup shape)
+    t.hist = (unsigned long long*)hist;
+    t.g = g;
+    t.lev = p ? (const double*)p->softlev.p : nullptr;
+    t.inv_w = inv_w;
+    t.bins = bins;
+    t.k_lo = k_lo;
+    t.k_hi = k_hi;
+    // (a generic-form layout that does not fit with the histogram: named, nothing was launched)
+    return rx_call("ofdm_rx_soft", p, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits, sym0, n_sym,
+                   n_valid_bits, counters, z_out, z_keep, [&](RxArgs& a, auto r) {
+                       return launch_rx_soft<decltype(r)>(p->logn, a, t, (hipStream_t)stream);
+                   },
+                   " with its 20 x 2 x " + std::to_string(bins) + " soft-decision histogram (" +
+                       std::to_string(4 * 2 * kSoftRows * bins) + " bytes)");
 }
 
 // ofdm_rx_sweep and ofdm_rx_sweep_frames (who; fr: the frame record of every point, or null -- without it

@@ -255,7 +255,7 @@ constexpr bool f64_rx_solo() {
 // __launch_bounds__ and in its `constexpr bool PROF, SWEEP, FRAMES, DENS` line, what the body
 // (ofdm_rx_body.hpp) sizes its workgroup and carves its LDS by, and what the launcher (rx_form_launch,
 // ofdm_kernels_inst.hpp) sizes, routes and launches by -- one description, so the three cannot disagree.
-enum class RxForm { Plain, Prof, Frames, Dens, Sweep, SweepFrames };
+enum class RxForm { Plain, Prof, Frames, Dens, Sweep, SweepFrames, Soft };
 template <RxForm F>
 struct RxFormOf {
     static constexpr bool PROF = F == RxForm::Prof;                               // k_rx_prof
@@ -263,7 +263,8 @@ struct RxFormOf {
     static constexpr bool FRAMES = F == RxForm::Frames || F == RxForm::SweepFrames;  // k_rx_frames, k_rx_sweep_frames
     static constexpr bool DENS = F == RxForm::Dens;                               // k_rx_dens
     // one wave per SIMD: the workgroup shape of rx_block / rx_waves / rx_carve (the reasons: rx_block)
-    static constexpr bool ONE_WAVE = PROF || SWEEP || DENS;
+    static constexpr bool SOFT = F == RxForm::Soft;                               // k_rx_soft
+    static constexpr bool ONE_WAVE = PROF || SWEEP || DENS || SOFT;
 };
 // MV: the complex128 SC-OFDM / zero-padding kernels (k_rx MV), ~10-50 VGPRs above their cyclic-prefix
 // OFDM twins: never the 4-wave shape, and the one-symbol N = 4096 shape at 2 waves per SIMD
@@ -1545,6 +1546,105 @@ __global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::Den
 #define OFDM_RX_BODY_DENS
 #include "ofdm_rx_body.hpp"
 #undef OFDM_RX_BODY_DENS
+}
+
+// The soft-decision record's LDS behind rx_carve's layout (k_rx_soft and its launcher): the plan's level
+// table, double[kMaxLuts][2][kSoftSide], then kSoftRows x 2 x B 32-bit bins
+struct SoftLds {
+    double* lev;
+    uint32_t* hist;
+};
+template <typename CV>
+__host__ __device__ __forceinline__ constexpr SoftLds soft_lds(CV& cv, int bins) {
+    SoftLds m{};
+    m.lev = cv.template take<double>((size_t)kMaxLuts * 2 * kSoftSide);
+    m.hist = cv.template take<uint32_t>((size_t)kSoftRows * 2 * bins);
+    return m;
+}
+// One element into the soft-decision histogram (ofdm_hip_soft.h, ofdm_rx_soft: the definition).  Per axis the
+// squared distances to the side levels, each fl(fl(c - lev) * fl(c - lev)) in double with no contraction,
+// and per bit of the axis the minimum over the levels whose index has the bit clear and set; then
+// D = fl(m1 - m0), u = fl(D * g), t = fl(u * inv_w), binned at B/2 + floor(t), clamped in double.  A
+// straight scan over the levels: the minima are exact selections, so their order does not matter, and a
+// NumPy restatement reproduces every double bit for bit.
+//   HBMAX: the most bits per axis the instantiation can meet (the loops' compile-time bound)
+//   lev: the LUT's [2][kSoftSide] levels in LDS; tidx: the transmitted index; cmask: its compared bits
+template <int HBMAX, typename R>
+__device__ __forceinline__ void soft_bin(cpx<R> v, int hb, uint32_t tidx, uint32_t cmask, const double* lev, double gk,
+                                         const RxSoftTail& st, uint32_t* hist, unsigned long long& invalid) {
+#pragma clang fp contract(off)
+    const int side = 1 << hb, half = st.bins >> 1;
+    const int row0 = hb * (hb - 1) + 2 * hb - 1;  // the row of index bit 0 (the last bit, MSB first)
+#pragma unroll
+    for (int ax = 0; ax < 2; ++ax) {
+        // ax = 0: the Q axis, index bits hb .. 2 hb - 1; ax = 1: the I axis, index bits 0 .. hb - 1
+        const double c = ax == 0 ? (double)v.im : (double)v.re;
+        const double* const l = lev + (ax == 0 ? kSoftSide : 0);
+        double m0[HBMAX], m1[HBMAX];
+#pragma unroll
+        for (int p = 0; p < HBMAX; ++p) m0[p] = m1[p] = (double)INFINITY;
+#pragma unroll
+        for (int a = 0; a < (1 << HBMAX); ++a) {
+            if (a < side) {
+                const double e = __dsub_rn(c, l[a]);
+                const double d = __dmul_rn(e, e);
+#pragma unroll
+                for (int p = 0; p < HBMAX; ++p) {
+                    if ((a >> p) & 1)
+                        m1[p] = __builtin_fmin(m1[p], d);
+                    else
+                        m0[p] = __builtin_fmin(m0[p], d);
+                }
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < HBMAX; ++p) {
+            const int pos = (ax == 0 ? hb : 0) + p;  // the bit's position in the index
+            if (p < hb && ((cmask >> pos) & 1u)) {
+                const double t = __dmul_rn(__dmul_rn(__dsub_rn(m1[p], m0[p]), gk), st.inv_w);
+                if (t != t) {
+                    ++invalid;
+                } else {
+                    double f = __builtin_floor(t);
+                    f = f < (double)-half ? (double)-half : f;
+                    f = f > (double)(half - 1) ? (double)(half - 1) : f;
+                    const int bin = half + (int)f;
+                    const int cell = ((row0 - pos) * 2 + (int)((tidx >> pos) & 1u)) * st.bins + bin;
+                    __hip_atomic_fetch_add(hist + cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+        }
+    }
+}
+
+// soft_bin out of line, for the generic kernel: inlined into its element loop the scan changes how the
+// compiler unswitches and schedules the loop, and with that which products of the complex64 equaliser
+// become FMAs -- the tap of k_rx_soft would differ from k_rx's in the last bit.  Behind a call the loop
+// keeps k_rx's arithmetic.
+template <typename R>
+__device__ __noinline__ void soft_bin_call(cpx<R> v, int hb, uint32_t tidx, uint32_t cmask, const double* lev, double gk,
+                                           const RxSoftTail& st, uint32_t* hist, unsigned long long& invalid) {
+    soft_bin<4, R>(v, hb, tidx, cmask, lev, gk, st, hist, invalid);
+}
+
+// The receiver that also accumulates the soft-decision record (ofdm_rx_soft, ofdm_hip_soft.h: the definition):
+// k_rx with the soft section compiled in.  Where the density bins the point, this form takes the same
+// point, the element's transmitted index (the one the symbol-error count compares) and its compared-bit
+// mask, and adds one count per compared bit to a [20][2][B] histogram of 32-bit bins in LDS behind the
+// receiver's own layout (soft_lds: the plan's level table staged in front of it).  Flushed and ended as
+// k_rx_dens' histogram is: one 64-bit integer atomic per non-empty bin and workgroup, a flush before a bin
+// could wrap (one iteration adds at most SPB * N to a bin), the NaN count a per-lane register.  Integers
+// only.  It takes the density's one-wave-per-SIMD shape, instantiations and routing; a WIDE plan has no
+// form (refused by the ABI).
+template <typename R, int LOGN, int EQ, int FB, bool MV, bool WIDE = false>
+__global__ __launch_bounds__((rx_block<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::Soft>::ONE_WAVE>()),
+                             (rx_waves<R, FB, LOGN, EQ, MV, RxFormOf<RxForm::Soft>::ONE_WAVE>())) void k_rx_soft(
+    RxArgs a, RxSoftTail st) {
+    using FORM = RxFormOf<RxForm::Soft>;
+    constexpr bool PROF = FORM::PROF, SWEEP = FORM::SWEEP, FRAMES = FORM::FRAMES, DENS = FORM::DENS, REF = false;
+#define OFDM_RX_BODY_SOFT
+#include "ofdm_rx_body.hpp"
+#undef OFDM_RX_BODY_SOFT
 }
 
 // The one-pass SNR sweep receiver (ofdm_rx_sweep): every symbol is received once per SNR point of the

@@ -255,7 +255,7 @@ static inline bool philox_streams(const RxArgs& a) {
 // (configs b, c: FB = 6), adaptive square-QAM loading at N = 2048 (config d: FB = 1), fixed 256-QAM at
 // N = 4096 (config e: FB = 8); 0 = no bench shape at this N and precision.  They are the shapes that have
 //   - REF instantiations of k_tx / k_rx (ref_shape: the caller's bits),
-//   - throughput forms of k_rx_prof, k_rx_frames and k_rx_dens (ofdm_record_inst.hpp: Philox streams),
+//   - throughput forms of k_rx_prof, k_rx_frames, k_rx_dens and k_rx_soft (ofdm_record_inst.hpp: Philox streams),
 //   - throughput forms of k_rx_sweep (ofdm_sweep_inst.hpp: the fixed-QAM ones, FB > 1, only).
 template <typename R, int LOGN>
 constexpr int ref_fb() { return sizeof(R) == 8 ? (LOGN == 10 ? 6 : LOGN == 11 ? 1 : LOGN == 12 ? 8 : 0) : 0; }
@@ -340,6 +340,7 @@ static auto rx_kernel() {
     else if constexpr (F == RxForm::Prof) return k_rx_prof<R, LOGN, EQ, FB, MV, false, WIDE>;
     else if constexpr (F == RxForm::Frames) return k_rx_frames<R, LOGN, EQ, FB, MV, WIDE>;
     else if constexpr (F == RxForm::Dens) return k_rx_dens<R, LOGN, EQ, FB, MV, WIDE>;
+    else if constexpr (F == RxForm::Soft) return k_rx_soft<R, LOGN, EQ, FB, MV, WIDE>;
     else if constexpr (F == RxForm::Sweep) return k_rx_sweep<R, LOGN, EQ, FB, MV>;
     else return k_rx_sweep_frames<R, LOGN, EQ, FB, MV>;
 }
@@ -354,7 +355,8 @@ static inline int rx_points(const RxSweepArgs& a) { return a.n_snr; }
 // a throughput layout that does not fit falls back to the generic kernel (EQ = -1, FB = 0, which builds
 // the modem variants in), and the generic kernel is the last resort: a shape it cannot hold is refused, not
 // launched (as tx_launch).  Then rx_go with the form's rounds.
-// a: RxArgs, or the sweeps' RxSweepArgs; tail: the kernel arguments behind it (RxFramesTail, RxDensTail)
+// a: RxArgs, or the sweeps' RxSweepArgs; tail: the kernel arguments behind it (RxFramesTail, RxDensTail,
+// RxSoftTail)
 template <RxForm F, typename R, int LOGN, int EQ, int FB, bool MV, bool REF = false, bool WIDE = false, typename A,
           typename... T>
 static hipError_t rx_form_launch(const A& a, hipStream_t s, T... tail) {
@@ -369,6 +371,8 @@ static hipError_t rx_form_launch(const A& a, hipStream_t s, T... tail) {
                                                   rx_points(a));
     // the histogram behind the receiver's own layout, as the kernel carves it
     if constexpr (FORM::DENS) (dens_lds(lds, tail.bins), ...);
+    // the soft record's level table and histogram likewise
+    if constexpr (FORM::SOFT) (soft_lds(lds, tail.bins), ...);
     constexpr size_t lut = FORM::PROF ? prof_lut_static<FB>() * sizeof(cpx<R>) : 0;
     if (lds.bytes + rx_static_lds<R, FB>() + lut > kLdsPerCu) {
         if constexpr (FB > 0) return rx_form_launch<F, R, LOGN, -1, 0, true>(a, s, tail...);
@@ -377,10 +381,12 @@ static hipError_t rx_form_launch(const A& a, hipStream_t s, T... tail) {
     // one iteration of a workgroup bins at most SPB * N points (<= 16384): the 32-bit bins are flushed
     // every `flush` iterations, before any of them could reach 2^32 (k_rx_dens) -- by the shape launched
     if constexpr (FORM::DENS) ((tail.flush = (uint32_t)(0xFFFFFFFFull / ((unsigned long long)G::SPB * G::N))), ...);
+    // (the soft record: one iteration puts at most one bit of each of its SPB * N elements into one bin)
+    if constexpr (FORM::SOFT) ((tail.flush = (uint32_t)(0xFFFFFFFFull / ((unsigned long long)G::SPB * G::N))), ...);
     // Two rounds of the resident workgroups where every workgroup ends with atomics of its own: up to five
     // per subcarrier (profile), up to one per bin (density), a pair per point behind a table per point
     // (the sweeps).  The frame record adds none per workgroup: k_rx's own grid.
-    constexpr int rounds = FORM::PROF || FORM::DENS || FORM::SWEEP ? 2 : rx_grid_rounds<R, FB, LOGN>();
+    constexpr int rounds = FORM::PROF || FORM::DENS || FORM::SWEEP || FORM::SOFT ? 2 : rx_grid_rounds<R, FB, LOGN>();
     return rx_go<BLK, G::SPB>(rx_kernel<F, R, LOGN, EQ, FB, MV, REF, WIDE>(), lds.bytes, rounds, c.n_sym, a, s, tail...);
 }
 

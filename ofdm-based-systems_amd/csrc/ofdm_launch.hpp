@@ -9,6 +9,7 @@
 
 #include "ofdm_device.hpp"
 #include "ofdm_hip.h"
+#include "ofdm_hip_soft.h"
 
 // Diagnostic ablation switches (timing studies: tools/ablate.py, tools/power_probe.py) exist only in
 // builds made with `make VARIANT=ablate EXTRA=-DOFDM_ABLATION=1`; the product library compiles
@@ -235,6 +236,25 @@ struct RxDensTail {
     uint32_t flush;
 };
 
+// ofdm_rx_soft: the soft-decision record's arguments, a second kernel parameter behind RxArgs (k_rx_soft
+// only; every other receiver takes its arguments alone, as before).  g and inv_w are what the host made
+// of the weights and the extent (ofdm_hip_soft.h): the kernel sees neither.
+//   lev: the plan's level table, double[n_luts][2][kSoftSide] -- per LUT the I levels LUT[a].re, then the Q
+//   levels LUT[a << hb].im, by index bits a (ofdm_abi.hip, plan creation); the kernel stages it in LDS
+//   flush: as RxDensTail's -- one iteration puts at most one bit of each element into one bin, so the
+//   launcher's floor((2^32 - 1) / (SPB * N)) iterations cannot wrap a 32-bit bin
+constexpr int kSoftSide = 16;                // levels per axis at most (256-QAM)
+constexpr int kSoftRows = OFDM_SOFT_ROWS;    // 2 + 4 + 6 + 8 bits of the four orders
+struct RxSoftTail {
+    unsigned long long* hist;  // device uint64[kSoftRows][2][bins] + 1 (last: invalid), accumulated
+    const double* g;           // device double[N]: the subcarrier's scale w_k / step_k^2
+    const double* lev;
+    double inv_w;
+    int bins;
+    int k_lo, k_hi;
+    uint32_t flush;
+};
+
 // ofdm_rx_sweep: the receiver's arguments (counters: device uint64[n_snr][2]; snr_lin, noise_on,
 // nr / ni, z_out, wide and profile of `r` unused: noise is always on) and the points' 10^(snr_db/10)
 struct RxSweepArgs {
@@ -328,6 +348,11 @@ hipError_t launch_rx_frames(int logn, const RxArgs& a, const RxFramesTail& f, hi
 // the receiver with the constellation-density record (ofdm_record_inst.hpp)
 template <typename R>
 hipError_t launch_rx_dens(int logn, const RxArgs& a, const RxDensTail& d, hipStream_t s);
+
+// the receiver with the soft-decision record (ofdm_record_inst.hpp); a plan with a PSK LUT or an order
+// above 256 is refused by the ABI before it
+template <typename R>
+hipError_t launch_rx_soft(int logn, const RxArgs& a, const RxSoftTail& t, hipStream_t s);
 
 // the one-pass SNR sweep receiver (ofdm_sweep_inst.hpp)
 template <typename R>

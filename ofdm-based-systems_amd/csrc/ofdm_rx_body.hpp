@@ -9,6 +9,9 @@
 // FRAMES and SWEEP (k_rx_sweep_frames only, which defines both macros and has `sa` and `ft` in scope): the
 // frame block runs inside the point loop, where bes / ses are the symbol's at the point, and adds them
 // to the point's rows of a point-major record, frames[pt][frame][2].
+// SOFT (k_rx_soft only, which defines OFDM_RX_BODY_SOFT around its include and has its second argument
+// `RxSoftTail st` in scope; FORM::SOFT): every compared bit of every element in range is also binned into
+// the soft-decision histogram in LDS, at the three places where DENS takes its point.
 // SWEEP (k_rx_sweep only, which defines OFDM_RX_BODY_SWEEP around its include and has its argument
 // `RxSweepArgs sa` in scope, `a` being sa.r): every symbol is received once per SNR
 // point, the point loop opened and closed under that macro so that the other kernels' text has no loop.
@@ -35,6 +38,13 @@
                   "the density record: the generic kernel, or a complex128 cyclic-prefix OFDM QAM throughput receiver");
 #else
     static_assert(!DENS, "k_rx_dens defines OFDM_RX_BODY_DENS around its include");
+#endif
+#ifdef OFDM_RX_BODY_SOFT
+    static_assert(FORM::SOFT && !REF && !WIDE && !PROF && !SWEEP && !FRAMES && !DENS &&
+                      (FB == 0 || (sizeof(R) == 8 && (FB == 1 || !(FB & 1)) && (FB == 1 || !MV))),
+                  "the soft record: the generic kernel, or a complex128 cyclic-prefix OFDM QAM throughput receiver");
+#else
+    static_assert(!FORM::SOFT, "k_rx_soft defines OFDM_RX_BODY_SOFT around its include");
 #endif
 #ifdef OFDM_RX_BODY_SWEEP
 #define OFDM_RX_SNR_LIN snr_lin_pt  // the SNR of the point being received
@@ -103,6 +113,27 @@
             if (c) {
                 atomicAdd(dt.hist + i, (unsigned long long)c);
                 if (zero) dhist[i] = 0;
+            }
+        }
+    };
+#endif
+#ifdef OFDM_RX_BODY_SOFT
+    // SOFT: the plan's level table and the workgroup's histogram behind the receiver's layout, the table
+    // staged and the bins zeroed before the first barrier
+    const SoftLds sl_ = soft_lds(cv, st.bins);
+    uint32_t* const shist = sl_.hist;
+    const int scells = kSoftRows * 2 * st.bins;
+    for (int i = threadIdx.x; i < scells; i += BLK) shist[i] = 0;
+    for (int i = threadIdx.x; i < cm.n_axis * 2 * kSoftSide; i += BLK) sl_.lev[i] = st.lev[i];
+    unsigned long long sinv = 0;  // the lane's NaN bits
+    uint32_t sleft = st.flush;    // iterations until the bins must be flushed (RxSoftTail)
+    // the workgroup's bins into the record: one 64-bit integer atomic per non-empty bin (between barriers)
+    auto soft_flush = [&](bool zero) {
+        for (int i = threadIdx.x; i < scells; i += BLK) {
+            const uint32_t c = shist[i];
+            if (c) {
+                atomicAdd(st.hist + i, (unsigned long long)c);
+                if (zero) shist[i] = 0;
             }
         }
     };
@@ -552,6 +583,34 @@
                         if (k >= dt.k_lo && k < dt.k_hi) dens_bin<R>(cscale(z[j], sc[j] * scale), dt, dhist, dout);
                     }
 #endif
+#ifdef OFDM_RX_BODY_SOFT
+                    // SOFT: the point k_rx_prof forms, the lane byte's transmitted index and the byte of the
+                    // valid-bit mask d was compared under (an order-0 subcarrier carries nothing)
+                    {
+                        uint32_t vmw = 0xFFFFFFFFu;
+                        if (!all_valid) {
+                            gptr<const uint64_t> scp = (gptr<const uint64_t>)cm.sc;
+                            vmw = 0;
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) {
+                                const ScInfo sc = __builtin_bit_cast(ScInfo, (uint64_t)scp[t + (4 * q + j) * TPS]);
+                                if (sc.lut < 0) continue;
+                                const int64_t nvb = a.n_valid_bits - (sbit + sc.bitoff);
+                                const int keep = nvb <= 0 ? 0 : (nvb >= sc.bits ? sc.bits : (int)nvb);
+                                vmw |= (((1u << keep) - 1u) << (sc.bits - keep)) << (8 * j);
+                            }
+                        }
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const int k = t + (4 * q + j) * TPS;
+                            const int lid = (int)((oc >> (8 * j)) & 0xFFu) / (int)sizeof(OP);
+                            if (lid == kUnusedOrder || k < st.k_lo || k >= st.k_hi) continue;
+                            const uint32_t ti = (lane_word(tb.lane, q) >> (8 * j)) & ((1u << axis[lid].bits) - 1u);
+                            soft_bin<4, R>(cscale(z[j], sc[j] * scale), (int)axis[lid].hbits, ti, (vmw >> (8 * j)) & 0xFFu,
+                                           sl_.lev + lid * 2 * kSoftSide, st.g[k], st, shist, sinv);
+                        }
+                    }
+#endif
                     if constexpr (PROF) {
                         // per element: the masked bit count from its byte of d; the error vector from
                         // z times its MMSE scale and the 1/sqrt(N) the slicer folds in, against the
@@ -608,6 +667,19 @@
                         const int k = t + (4 * q + j) * TPS;
                         if (k >= dt.k_lo && k < dt.k_hi)
                             dens_bin<R>(cscale(z[j], fold ? sc[j] * scale : scale), dt, dhist, dout);
+                    }
+#endif
+#ifdef OFDM_RX_BODY_SOFT
+                    // SOFT: the point k_rx_prof forms and the lane byte's transmitted index, every bit compared
+                    if constexpr (!FB_PSK_ONLY) {
+                        const uint32_t stx = lane_word(tb.lane, q) & PermSlicer<FB>::BYTE_MASK;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const int k = t + (4 * q + j) * TPS;
+                            if (k >= st.k_lo && k < st.k_hi)
+                                soft_bin<FB / 2, R>(cscale(z[j], fold ? sc[j] * scale : scale), FB / 2, (stx >> (8 * j)) & 0xFFu,
+                                                    0xFFu, sl_.lev, st.g[k], st, shist, sinv);
+                        }
                     }
 #endif
                     if constexpr (PROF) {
@@ -672,6 +744,20 @@
                         d &= ((1u << keep) - 1u) << (b - keep);
                     }
                     bes += __popc(d);
+#ifdef OFDM_RX_BODY_SOFT
+                    // SOFT: the value the tap stores, the transmitted index and the mask d was compared under
+                    // (b / 2 outside 1 .. 4: a memory-safety guard only -- the ABI refuses such a plan, soft_ok)
+                    if (k >= st.k_lo && k < st.k_hi && b >= 2 && b <= 8 && !(b & 1)) {
+                        uint32_t cmask = 0xFFu;
+                        if (!all_valid) {
+                            const int64_t nvb = a.n_valid_bits - (sbit + off);
+                            const int keep = nvb <= 0 ? 0 : (nvb >= b ? b : (int)nvb);
+                            cmask = ((1u << keep) - 1u) << (b - keep);
+                        }
+                        soft_bin_call<R>(v, b >> 1, tidx, cmask, sl_.lev + (adaptive ? (int)cm.sc[k].lut : 0) * 2 * kSoftSide, st.g[k],
+                                         st, shist, sinv);
+                    }
+#endif
                     if constexpr (PROF) {
                         // error vector against the transmitted point (the plan's LUT pool, plan
                         // precision), its power capped at kProfCap so that fx_accum's share stays
@@ -750,6 +836,15 @@
             dleft = dt.flush;
         }
 #endif
+#ifdef OFDM_RX_BODY_SOFT
+        // SOFT: as DENS -- before a 32-bit bin could wrap, the bins go to the record and start again
+        if (--sleft == 0) {
+            __syncthreads();
+            soft_flush(true);
+            __syncthreads();
+            sleft = st.flush;
+        }
+#endif
         sym_sync<TPS>();  // W and the FFT row are rewritten by the next symbol
 #ifdef OFDM_RX_BODY_SWEEP
         }  // (the point loop: the next point's FFT rewrites the row too)
@@ -767,6 +862,13 @@
     dens_flush(false);
     dout = block_sum<unsigned long long, BLK>(dout, redc);
     if (threadIdx.x == 0 && dout) atomicAdd(dt.hist + dcells, dout);
+#endif
+#ifdef OFDM_RX_BODY_SOFT
+    // SOFT: the workgroup's bins and its NaN count into the record
+    __syncthreads();
+    soft_flush(false);
+    sinv = block_sum<unsigned long long, BLK>(sinv, redc);
+    if (threadIdx.x == 0 && sinv) atomicAdd(st.hist + scells, sinv);
 #endif
 #ifdef OFDM_RX_BODY_SWEEP
     // (be and se are zero here, and block_sum's barriers stand between the points' LDS sums and this

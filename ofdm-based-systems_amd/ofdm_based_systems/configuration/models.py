@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Literal, Optional
+from typing import List, Literal, Optional, Union
 
 from pydantic import BaseModel, Field, field_validator
 
@@ -87,6 +87,13 @@ class SimulationSettings(BaseSettings):
     constellation_density_extent: Optional[float] = Field(None, gt=0, description="half-width L of the density's "
                                                           "square [-L, L)^2 (None: 1.5 times the constellation's "
                                                           "largest coordinate)")
+    soft_bins: Optional[int] = Field(None, ge=2, le=256, multiple_of=2, description="bins (even): also report the "
+                                     "soft decisions of the whole run -- the per-bit max-log LLR histograms and "
+                                     "the bit-wise mutual information (None: no soft record)")
+    soft_extent: Optional[float] = Field(None, gt=0, description="half-width L of the soft histograms, in squared "
+                                         "minimum distances (None: 8)")
+    soft_weights: Optional[Union[str, List[float]]] = Field(None, description="per-subcarrier weights of the soft "
+                                                            "values: None, \"csi\" or one weight per subcarrier")
 
     def __str__(self) -> str:
         lines = [

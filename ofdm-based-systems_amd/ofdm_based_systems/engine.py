@@ -48,6 +48,11 @@ Constellation density: ``run(..., density=G)`` also bins every equalised point o
 grid over a square of the I/Q plane (ofdm_rx_density: 32-bit bins in LDS per workgroup, integer atomics
 into a uint64 record behind the counters); :class:`ConstellationDensity` carries it.
 
+Soft decisions: ``run(..., soft=B)`` also bins, for every compared bit, the max-log distance difference
+in units of the subcarrier's squared minimum distance into a histogram conditioned on the transmitted bit
+(ofdm_rx_soft: integers, behind the counters like the density); :class:`SoftDecisions` carries it and
+computes the LLR histograms and the bit-wise mutual information (GMI) from it on the host.
+
 PAPR distribution: :meth:`LinkEngine.papr` bins the per-symbol PAPR of the stream ``run`` transmits
 (ofdm_papr: the transmitter's map and IFFT, no channel, no receiver) into an integer histogram on the
 device; :class:`PaprStats` carries it and its CCDF.
@@ -215,6 +220,169 @@ def density_grid(bins, extent) -> tuple:
     return -L, int(bins) / (2.0 * L)
 
 
+def soft_grid(bins, extent=8.0) -> float:
+    """inv_w = B / (2 L) of ofdm_rx_soft's histograms: B bins over [-L, L) in units of the subcarrier's
+    squared minimum distance, formed here in double (the library never sees L).  B is even, so zero is a
+    bin line.  ValueError for a B that is not an even number in [2, B.MAX_SOFT_BINS] or an L that is not
+    finite and positive."""
+    if isinstance(bins, bool) or int(bins) != bins or not 2 <= int(bins) <= B.MAX_SOFT_BINS or int(bins) % 2:
+        raise ValueError(f"soft = {bins!r} is not an even number of bins in [2, {B.MAX_SOFT_BINS}] "
+                         "(more than 256 bins are not built)")
+    L = float(extent)
+    if not (math.isfinite(L) and L > 0.0):
+        raise ValueError(f"soft_extent = {extent!r} is not a finite positive extent")
+    return int(bins) / (2.0 * L)
+
+
+def soft_orders(luts: Sequence[np.ndarray]) -> None:
+    """ValueError unless every LUT is a separable square QAM of order 4, 16, 64 or 256 -- LUT[i] =
+    I[i & (side - 1)] + j Q[i >> hb] -- the constellations the soft record is built for."""
+    for l in luts:
+        l = np.asarray(l, np.complex128)
+        m = len(l)
+        if m > 256:
+            raise ValueError(f"soft: a constellation above 256 points ({m}) has no soft record (not built)")
+        hb = (m.bit_length() - 1) // 2
+        sq = m in (4, 16, 64, 256) and np.array_equal(l.reshape(1 << hb, 1 << hb).real, np.tile(l[:1 << hb].real, (1 << hb, 1))) \
+            and np.array_equal(l.reshape(1 << hb, 1 << hb).imag, np.tile(l[::1 << hb].imag[:, None], (1, 1 << hb))) \
+            and len(np.unique(l[:1 << hb].real)) == 1 << hb and len(np.unique(l[::1 << hb].imag)) == 1 << hb
+        if not sq:
+            raise ValueError(f"soft: a non-separable (PSK) or non-square constellation of {m} points has no soft "
+                             "record (not built: square QAM of order 4, 16, 64 or 256 only)")
+
+
+def soft_scale(luts: Sequence[np.ndarray], sc_lut, weights, h_raw, n_fft: int) -> np.ndarray:
+    """float64 [N]: ofdm_rx_soft's scale table g[k] = w_k / step_k^2.  step_k = (max I level - min I
+    level) / (side - 1) of subcarrier k's LUT, in double; an inactive subcarrier has g = 0.  ``weights``:
+    None: w = 1; "csi": w_k = |H_k|^2 / max |H|^2 with H = fft(h_raw, N), the equaliser's H; an array of N
+    finite non-negative floats: taken as given.  ValueError for anything else."""
+    soft_orders(luts)
+    N = int(n_fft)
+    inv2 = []
+    for l in luts:
+        re = np.asarray(l, np.complex128).real
+        side = 1 << ((len(l).bit_length() - 1) // 2)
+        step = (float(re.max()) - float(re.min())) / (side - 1)
+        inv2.append(1.0 / (step * step))
+    inv2 = np.array(inv2, np.float64)
+    if sc_lut is None:
+        base = np.full(N, inv2[0], np.float64)
+    else:
+        sc = np.asarray(sc_lut, np.int64)
+        base = np.where(sc >= 0, inv2[np.maximum(sc, 0)], 0.0)
+    if weights is None:
+        w = np.ones(N, np.float64)
+    elif isinstance(weights, str):
+        if weights != "csi":
+            raise ValueError(f"soft_weights = {weights!r} is not None, \"csi\" or an array of {N} weights")
+        p = np.abs(np.fft.fft(np.asarray(h_raw, np.complex128), N)) ** 2
+        top = float(p.max())
+        if not (math.isfinite(top) and top > 0.0):
+            raise ValueError("soft_weights = \"csi\": the channel response has no finite positive maximum")
+        w = p / top
+    else:
+        w = np.asarray(weights, np.float64)
+        if w.shape != (N,) or not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError(f"soft_weights is not None, \"csi\" or an array of {N} finite non-negative floats")
+    return np.ascontiguousarray(w * base, dtype=np.float64)
+
+
+@dataclass
+class SoftDecisions:
+    """The soft decisions of a whole run (``ofdm_rx_soft``, include/ofdm_hip.h): for every compared bit the
+    max-log distance difference D = min over the points with bit 1 - min over the points with bit 0 of the
+    squared distance, per axis, times the subcarrier's weight over its squared level spacing, binned into B
+    bins over [-extent, extent) (the end bins saturate) and conditioned on the transmitted bit.  A positive
+    value favours bit 0.  Accumulated on the device in integers: identical for any batching and rank count.
+    Row (b/2)(b/2 - 1) + i holds bit i (MSB first) of the subcarriers with b bits."""
+    counts: np.ndarray     # int64 [20][2][B]: row, transmitted bit, bin
+    invalid: int           # bits whose value was NaN (a ZF point on a null bin)
+    bins: int              # B
+    extent: float          # L
+    subcarriers: tuple     # (k_lo, k_hi): the subcarriers counted, [k_lo, k_hi)
+    n_bits: int            # counts.sum() + invalid: the compared bits in range
+
+    ORDERS = (2, 4, 6, 8)  # bits per subcarrier of the orders the record has rows for
+
+    @staticmethod
+    def row0(b: int) -> int:
+        if b not in SoftDecisions.ORDERS:
+            raise ValueError(f"b = {b!r} is not 2, 4, 6 or 8 bits per subcarrier")
+        return (b // 2) * (b // 2 - 1)
+
+    def rows(self, b: int) -> np.ndarray:
+        """int64 [b][2][B]: the rows of the subcarriers with b bits, bit 0 (the MSB) first."""
+        return self.counts[self.row0(b):self.row0(b) + b]
+
+    @property
+    def orders(self) -> tuple:
+        """The b whose rows hold anything."""
+        return tuple(b for b in self.ORDERS if self.rows(b).any())
+
+    @property
+    def hard_bit_errors(self) -> int:
+        """The mass on the wrong side of zero: tx bit 0 in bins < B/2 plus tx bit 1 in bins >= B/2 -- the
+        hard decisions' bit errors, as long as no value is exactly undecided."""
+        h = self.bins // 2
+        return int(self.counts[:, 0, :h].sum() + self.counts[:, 1, h:].sum())
+
+    @property
+    def llr_centres(self) -> np.ndarray:
+        """float64 [B]: the bin centres (j - B/2 + 0.5) 2 L / B, in the record's unit."""
+        return (np.arange(self.bins, dtype=np.float64) - self.bins / 2 + 0.5) * (2.0 * self.extent / self.bins)
+
+    def _row_info(self, rows: np.ndarray, s: float) -> np.ndarray:
+        """float64 [rows]: 1 - sum counts log2(1 + exp(-(1 - 2 v) s centre)) / n_row (0 for an empty row)."""
+        x = s * self.llr_centres
+        pen = np.stack([np.logaddexp(0.0, -x), np.logaddexp(0.0, x)]) / math.log(2.0)  # [tx bit][bin]
+        n = rows.sum(axis=(1, 2)).astype(np.float64)
+        loss = (rows * pen[None]).sum(axis=(1, 2))
+        return np.where(n > 0, 1.0 - loss / np.maximum(n, 1.0), 0.0)
+
+    def gmi_scale(self, b: int) -> float:
+        """The s >= 0 in [1e-2, 1e3] that maximises the order's GMI: a golden-section search on log s (the
+        sum is concave in s, so it has one maximum)."""
+        rows = self.rows(b)
+        f = lambda t: float(self._row_info(rows, math.exp(t)).sum())
+        lo, hi = math.log(1e-2), math.log(1e3)
+        q = (math.sqrt(5.0) - 1.0) / 2.0
+        x1, x2 = hi - q * (hi - lo), lo + q * (hi - lo)
+        f1, f2 = f(x1), f(x2)
+        for _ in range(80):
+            if f1 < f2:
+                lo, x1, f1 = x1, x2, f2
+                x2 = lo + q * (hi - lo)
+                f2 = f(x2)
+            else:
+                hi, x2, f2 = x2, x1, f1
+                x1 = hi - q * (hi - lo)
+                f1 = f(x1)
+        cands = [math.log(1e-2), 0.5 * (lo + hi), math.log(1e3)]
+        return math.exp(max(cands, key=f))
+
+    def gmi_per_bit(self, b: int, scale: Optional[float] = None) -> np.ndarray:
+        """float64 [b]: the mutual information of each bit of the subcarriers with b bits, in bits (the
+        mismatched-decoding GMI of the binned values read as LLRs s * value; ``scale`` None: the s that
+        maximises their sum)."""
+        s = self.gmi_scale(b) if scale is None else float(scale)
+        return self._row_info(self.rows(b), s)
+
+    def gmi(self, b: Optional[int] = None, scale: Optional[float] = None) -> float:
+        """The bit-wise mutual information (BICM rate) in bits per subcarrier use of the subcarriers with b
+        bits: sum over their rows of 1 - sum counts log2(1 + exp(-(1 - 2 v) s centre)) / n_row, with
+        ``scale`` None at the s >= 0 that maximises it -- it needs no noise variance.  b None: over every
+        order of the run, the total rate per OFDM symbol divided by the active subcarriers, one s per order
+        (a run of one order: that order's)."""
+        if b is not None:
+            return float(self.gmi_per_bit(b, scale).sum())
+        # subcarrier uses of an order: the bits of its first row
+        use = {o: int(self.rows(o)[0].sum()) for o in self.ORDERS}
+        total = sum(use.values())
+        if total == 0:
+            return 0.0
+        return float(sum(use[o] * self.gmi(o, scale) for o in self.ORDERS if use[o]) / total)
+
+
 @dataclass
 class LinkStats:
     bit_errors: int
@@ -234,6 +402,7 @@ class LinkStats:
     clip_samples: Optional[int] = None     # samples examined: N per OFDM symbol
     frames: Optional[FrameStats] = None    # run(..., frame_symbols=F)
     density: Optional[ConstellationDensity] = None  # run(..., density=G)
+    soft: Optional[SoftDecisions] = None   # run(..., soft=B)
 
 
 def default_papr_edges_db() -> np.ndarray:
@@ -417,6 +586,19 @@ def _density_record(grid: tuple, subcarriers: tuple) -> _Record:
                    lambda rec: {"density": rec, "density_params": grid, "density_subcarriers": subcarriers}, decode)
 
 
+def _soft_record(g, inv_w: float, bins: int, extent: float, subcarriers: tuple) -> _Record:
+    """ofdm_rx_soft's record, int64 [20 * 2 * B + 1]; g: the device scale table of :func:`soft_scale`."""
+    Bn = int(bins)
+    cells = B.SOFT_ROWS * 2 * Bn
+
+    def decode(rec, n_sym):
+        return SoftDecisions(counts=rec[:cells].reshape(B.SOFT_ROWS, 2, Bn).copy(), invalid=int(rec[cells]), bins=Bn,
+                             extent=extent, subcarriers=subcarriers, n_bits=int(rec.sum()))
+
+    return _Record((cells + 1,), "ofdm_rx_soft", "soft",
+                   lambda rec: {"soft": rec, "soft_params": (g, inv_w, Bn), "soft_subcarriers": subcarriers}, decode)
+
+
 class LinkEngine:
     plan = None    # the libofdm_hip plan (set by __init__)
     _fused = None  # has_fused, asked of the library once per engine
@@ -465,6 +647,8 @@ class LinkEngine:
         the channel) at ``clip_db`` dB above the nominal mean power of a time sample
         (:func:`nominal_sample_power`); None: a linear transmitter."""
         self._nominal = (n_fft, list(luts), sc_lut)
+        # what a soft record's scale table is made of (soft_scale)
+        self._soft_src = (list(luts), sc_lut, np.asarray(h_raw, np.complex128))
         # max over the LUT pool of max(|re|, |im|): the default extent of a density record is 1.5 of it
         self.lut_reach = max(float(max(np.max(np.abs(np.real(l))), np.max(np.abs(np.imag(l))))) for l in luts)
         if clip_db is not None:
@@ -532,15 +716,24 @@ class LinkEngine:
 
     def rx(self, stream, y, nr, ni, seed, stats, total_samples, snr_db, noise_on, bits_d, sym0, n_sym,
            n_valid, counters, z_out=None, z_keep=0, profile=None, frames=None, frame_symbols=None,
-           density=None, density_params=None, density_subcarriers=None):
+           density=None, density_params=None, density_subcarriers=None,
+           soft=None, soft_params=None, soft_subcarriers=None):
         """ofdm_rx, or with a profile record (device int64 [5][N]) ofdm_rx_profile, or with a frame
         record (``frames``: device int64 [n_frames][2] of the whole run, ``frame_symbols`` OFDM symbols
         per frame) ofdm_rx_frames, or with a density record (``density``: device int64 [G * G + 1],
-        ``density_params``: (lo, inv_w, G), ``density_subcarriers``: (k_lo, k_hi)) ofdm_rx_density."""
+        ``density_params``: (lo, inv_w, G), ``density_subcarriers``: (k_lo, k_hi)) ofdm_rx_density, or with a
+        soft record (``soft``: device int64 [40 B + 1], ``soft_params``: (g: device float64 [N], inv_w, B),
+        ``soft_subcarriers``: (k_lo, k_hi)) ofdm_rx_soft."""
         args = (self.plan.handle, stream, B.ptr(y), B.ptr(nr), B.ptr(ni), int(seed), B.ptr(stats),
                 int(total_samples), float(snr_db), int(noise_on), B.ptr(bits_d), int(sym0), int(n_sym),
                 int(n_valid), B.ptr(counters), B.ptr(z_out), int(z_keep))
-        if density is not None:
+        if soft is not None:
+            if profile is not None or frames is not None or density is not None:
+                raise ValueError("rx: a soft record together with another record has no kernel")
+            g, inv_w, bins = soft_params
+            B.check(self._lib.ofdm_rx_soft(*args, B.ptr(g), float(inv_w), int(bins), int(soft_subcarriers[0]),
+                                           int(soft_subcarriers[1]), B.ptr(soft)))
+        elif density is not None:
             if profile is not None or frames is not None:
                 raise ValueError("rx: a density record together with a profile or a frame record has no kernel")
             lo, inv_w, G = density_params
@@ -667,7 +860,7 @@ class LinkEngine:
         if fused and not can:
             raise ValueError("no fused form for this run: ofdm_link takes a complex128 N = 1024 fixed 64-QAM "
                              "cyclic-prefix OFDM plan over a flat channel without equaliser, Philox streams, "
-                             "no received-symbol tap, no profile, frame record or density record and every bit compared, and no clip level "
+                             "no received-symbol tap, no profile, frame record, density record or soft record and every bit compared, and no clip level "
                              "(clip_db: the limiter is not built into k_link)")
         return can if fused is None else bool(fused)
 
@@ -805,7 +998,9 @@ class LinkEngine:
                   profile: bool = False, fused: Optional[bool] = None,
                   frame_symbols: Optional[int] = None, density: Optional[int] = None,
                   density_extent: Optional[float] = None,
-                  density_subcarriers: Optional[tuple] = None) -> "PendingLink":
+                  density_subcarriers: Optional[tuple] = None, soft: Optional[int] = None,
+                  soft_extent: Optional[float] = None, soft_weights=None,
+                  soft_subcarriers: Optional[tuple] = None) -> "PendingLink":
         """Enqueue global OFDM symbols [0, n_sym) (this rank's shard when ``group`` is set) on
         the current stream without waiting for them; :meth:`PendingLink.result` reads the
         counts back.  Back-to-back calls therefore keep the GPU busy while the host prepares
@@ -847,6 +1042,16 @@ class LinkEngine:
                   any run is the same for every batching and rank count, exactly.  Not together with
                   ``profile`` or ``frame_symbols``; the fused route has no record (None takes the
                   two-kernel path).
+        soft    : B: accumulate the soft decisions of the whole run (LinkStats.soft, :class:`SoftDecisions`):
+                  for every compared bit the max-log distance difference, in units of the subcarrier's
+                  squared minimum distance, binned into B bins (even, <= B.MAX_SOFT_BINS) over [-L, L) and
+                  conditioned on the transmitted bit, int64 [20][2][B] + 1 behind the counters (the last
+                  word counts NaN values).  ``soft_extent``: L (default 8); ``soft_weights``: None, "csi"
+                  (|H_k|^2 / max |H|^2) or N non-negative floats (:func:`soft_scale`);
+                  ``soft_subcarriers``: (k_lo, k_hi).  Square QAM of order 4 to 256 only, fixed or
+                  adaptive.  ofdm_rx_soft, routed as the density (a run with a tap: the generic receiver on
+                  all its batches).  Not together with ``profile``, ``frame_symbols`` or ``density``; the
+                  fused route has no record (None takes the two-kernel path).
         fused   : the route.  None: the fused one -- a power pass, then one ofdm_link launch that
                   transmits and receives every symbol of the shard in registers: no y buffer, no
                   batching -- when the plan has a fused form (has_fused), the streams are Philox
@@ -876,12 +1081,30 @@ class LinkEngine:
                                  f"0 <= k_lo < k_hi <= {self.n_fft}")
         elif density_extent is not None or density_subcarriers is not None:
             raise ValueError("density_extent / density_subcarriers without density")
+        sgrid = None
+        if soft is not None:
+            for other, name in ((profile, "profile=True"), (frame_symbols is not None, "frame_symbols"),
+                                (density is not None, "density")):
+                if other:
+                    raise ValueError(f"{name} together with soft: the receiver with both records is not built; "
+                                     "run twice")
+            sL = 8.0 if soft_extent is None else float(soft_extent)
+            sgrid = (soft_grid(soft, sL), int(soft), sL)
+            srange = (0, self.n_fft) if soft_subcarriers is None else tuple(int(k) for k in soft_subcarriers)
+            if len(srange) != 2 or not 0 <= srange[0] < srange[1] <= self.n_fft:
+                raise ValueError(f"soft_subcarriers = {soft_subcarriers!r} is not a range "
+                                 f"0 <= k_lo < k_hi <= {self.n_fft}")
+            luts, sc_lut, h_raw = self._soft_src
+            g_host = soft_scale(luts, sc_lut, soft_weights, h_raw, self.n_fft)  # (PSK, wide plans: ValueError)
+        elif soft_extent is not None or soft_weights is not None or soft_subcarriers is not None:
+            raise ValueError("soft_extent / soft_weights / soft_subcarriers without soft")
         r = self._share(n_sym, group, n_valid_bits)
         dev, N = r.dev, self.n_fft
         # the run's record, at most one (the pairs were refused above)
         rec = (_profile_record(N, self.bits_per_subcarrier) if profile else
                _frames_record(n_frames, frame_symbols, self.bps, r.n_valid) if n_frames else
-               _density_record(dgrid, drange) if dgrid else None)
+               _density_record(dgrid, drange) if dgrid else
+               _soft_record(self.upload(g_host), sgrid[0], sgrid[1], sgrid[2], srange) if sgrid else None)
         use_link = self._route_fused(fused, philox=bits is None and normals is None, tap=keep_symbols > 0,
                                      profile=rec is not None, whole=r.n_valid >= n_sym * self.bps)
 
@@ -902,7 +1125,7 @@ class LinkEngine:
             zk = keep if sym0 == r.lo else 0  # the tap: the shard's first symbols, so its first batch
             # (a density record: the later batches of a run with a tap keep the tap buffer, z_keep = 0, so
             # that every batch takes the generic receiver -- one form per run, ofdm_rx_density)
-            zo = z_out if zk or dgrid else None
+            zo = z_out if zk or dgrid or sgrid else None
             self._timed(events if resident else None, rx_name, n, lambda: self.rx(
                 r.stream, y, nr_d, ni_d, seed, stats, r.samples, snr_db, noise_on, bits_d, sym0, n, r.n_valid,
                 counters, zo, zk, **pkw))
@@ -924,7 +1147,8 @@ class LinkEngine:
     def run_sweep_async(self, n_sym: int, snr_dbs, *, seed: int = 0, group=None,
                         y_budget: int = DEFAULT_Y_BUDGET, batch: Optional[int] = None,
                         n_valid_bits: Optional[int] = None, events: Optional[list] = None,
-                        frame_symbols: Optional[int] = None, density: Optional[int] = None) -> "PendingSweep":
+                        frame_symbols: Optional[int] = None, density: Optional[int] = None,
+                        soft: Optional[int] = None) -> "PendingSweep":
         """Throughput-mode (Philox) runs of global OFDM symbols [0, n_sym) at every SNR of
         ``snr_dbs`` with one seed, from one transmit: point k is ``run(n_sym, snr_dbs[k], seed=seed)``
         -- the same bits, noise words, sigma and per-sample arithmetic, so in complex128 the same
@@ -940,6 +1164,9 @@ class LinkEngine:
         (``frame_symbols``: ValueError -- :meth:`run_frame_sweep_async` is the sweep with one), a density
         record (``density``: ValueError), a received-symbol tap, and a plan per point (adaptive loading
         re-derived per SNR)."""
+        if soft is not None:
+            raise ValueError("run_sweep with soft: the sweep receiver keeps no soft record "
+                             "(the soft decisions inside k_rx_sweep are not built); use run per point")
         if density is not None:
             raise ValueError("run_sweep with density: the sweep receiver keeps no density record "
                              "(the density inside k_rx_sweep is not built); use run per point")
@@ -956,7 +1183,8 @@ class LinkEngine:
 
     def run_frame_sweep_async(self, n_sym: int, snr_dbs, frame_symbols: int, *, seed: int = 0, group=None,
                               y_budget: int = DEFAULT_Y_BUDGET, batch: Optional[int] = None,
-                              n_valid_bits: Optional[int] = None, events: Optional[list] = None) -> "PendingSweep":
+                              n_valid_bits: Optional[int] = None, events: Optional[list] = None,
+                              soft: Optional[int] = None) -> "PendingSweep":
         """:meth:`run_sweep_async` with the per-frame error record of every point: point k is
         ``run(n_sym, snr_dbs[k], seed=seed, frame_symbols=F)`` -- its counters as :meth:`run_sweep`
         gives them, and ``.frames`` the :class:`FrameStats` that run builds, with the same
@@ -972,6 +1200,9 @@ class LinkEngine:
         ValueError before any launch: a bad F or too many frames (:func:`frame_count`), more than
         B.MAX_FRAMES rows over all points (the 256 MiB cap on the whole record), an empty list, a
         non-finite point; otherwise what :meth:`run_sweep_async` does not take is not taken here."""
+        if soft is not None:
+            raise ValueError("run_frame_sweep with soft: the sweep receiver keeps no soft record "
+                             "(the soft decisions inside k_rx_sweep_frames are not built); use run per point")
         return self._sweep_async("run_frame_sweep", n_sym, snr_dbs, frame_symbols, seed=seed, group=group,
                                  y_budget=y_budget, batch=batch, n_valid_bits=n_valid_bits, events=events)
 
@@ -1022,7 +1253,7 @@ class LinkEngine:
     def run_pipelined(self, n_sym: int, snr_db, seeds, *, group=None,
                       events: Optional[list] = None, y_budget: int = DEFAULT_Y_BUDGET, lanes: int = 1,
                       fused: Optional[bool] = None, frame_symbols: Optional[int] = None,
-                      density: Optional[int] = None) -> list:
+                      density: Optional[int] = None, soft: Optional[int] = None) -> list:
         """Independent throughput-mode runs (one per seed) of global OFDM symbols [0, n_sym),
         software-pipelined across runs: run k+1's TX is enqueued before run k's RX, so with
         several ranks the statistics exchange of run k (the one collective on a run's
@@ -1048,6 +1279,9 @@ class LinkEngine:
                              "record; use run_async or run_sweep")
         if frame_symbols is not None:
             raise ValueError("run_pipelined with frame_symbols: the pipelined schedule carries no frame record; "
+                             "use run_async")
+        if soft is not None:
+            raise ValueError("run_pipelined with soft: the pipelined schedule carries no soft record; "
                              "use run_async")
         if density is not None:
             raise ValueError("run_pipelined with density: the pipelined schedule carries no density record; "

@@ -143,8 +143,22 @@ class Simulation:
         frame_symbols: Optional[int] = None,
         constellation_density: Optional[int] = None,
         constellation_density_extent: Optional[float] = None,
+        soft_bins: Optional[int] = None,
+        soft_extent: Optional[float] = None,
+        soft_weights=None,
     ):
-        """constellation_density: G: also return where the received points of the whole run fall in the
+        """soft_bins: B: also return the soft decisions of the whole run -- for every compared bit the max-log
+        distance difference, in units of the subcarrier's squared minimum distance (times ``soft_weights``:
+        None, "csi" or one weight per subcarrier), binned on the GPU into B bins (even, <= 256) over
+        [-L, L), L = ``soft_extent`` (default 8), conditioned on the transmitted bit
+        (engine.SoftDecisions, ``LinkEngine.run(soft=B)``, ofdm_rx_soft): the key ``soft_decisions`` =
+        {``bins``, ``extent``, ``counts`` (nested lists [20][2][B]), ``invalid``, ``num_bits``,
+        ``gmi_bits_per_subcarrier``, ``gmi_scale`` (bits per subcarrier -> the LLR scale chosen)}.  Without
+        it the result dict is unchanged.  Square QAM only; needs the fused path (the built-in modulators,
+        prefixes and constellations); not combined with ``subcarrier_profile``, ``frame_symbols``,
+        ``constellation_density`` or ``run_sweep``.
+
+        constellation_density: G: also return where the received points of the whole run fall in the
         I/Q plane -- every equalised point binned on the GPU into a G x G grid (G <= 128) over the square
         [-L, L)^2, L = ``constellation_density_extent`` (default 1.5 times the constellation's largest
         coordinate) (engine.ConstellationDensity, ``LinkEngine.run(density=G)``, ofdm_rx_density): the key
@@ -221,6 +235,9 @@ class Simulation:
         self.frame_symbols = frame_symbols
         self.constellation_density = constellation_density
         self.constellation_density_extent = constellation_density_extent
+        self.soft_bins = soft_bins
+        self.soft_extent = soft_extent
+        self.soft_weights = soft_weights
 
     def _log(self, message: str) -> None:
         if self.verbose:
@@ -246,7 +263,8 @@ class Simulation:
         extra = {"rng_mode": s.rng_mode, "seed": s.seed, "precision": s.precision,
                  "batch_symbols": s.batch_symbols, "clip_db": s.clip_db, "frame_symbols": s.frame_symbols,
                  "constellation_density": s.constellation_density,
-                 "constellation_density_extent": s.constellation_density_extent}
+                 "constellation_density_extent": s.constellation_density_extent,
+                 "soft_bins": s.soft_bins, "soft_extent": s.soft_extent, "soft_weights": s.soft_weights}
         return [
             cls(num_bits=s.num_bits, num_symbols=s.num_symbols, num_subcarriers=s.num_bands,
                 constellation_order=s.constellation_order, constellation_scheme=s.constellation_type,
@@ -370,6 +388,10 @@ class Simulation:
             raise ValueError(f"{who} with constellation_density: the sweep receiver keeps no density record; "
                              "run the simulations one by one")
 
+        if s0.soft_bins is not None:
+            raise ValueError(f"{who} with soft_bins: the sweep receiver keeps no soft record; "
+                             "run the simulations one by one")
+
         swept: List[Any] = []  # the engine sweep's LinkStats, filled by the first simulation
 
         def link(k):
@@ -434,6 +456,19 @@ class Simulation:
         if self.frame_symbols is not None:
             raise ValueError("constellation_density with frame_symbols: the receiver with both records is not built")
 
+    def _check_soft(self) -> None:
+        """What a soft record is not combined with, refused before the run: user-supplied strategy classes
+        (the composed path keeps no record), the other records, a bad B or L."""
+        from ofdm_based_systems.engine import soft_grid
+
+        soft_grid(self.soft_bins, 8.0 if self.soft_extent is None else self.soft_extent)  # (ValueError)
+        if not self._builtin_strategies():
+            raise ValueError("soft_bins needs the built-in modulators, prefixes and constellations")
+        for other, name in ((self.subcarrier_profile, "subcarrier_profile"), (self.frame_symbols is not None, "frame_symbols"),
+                            (self.constellation_density is not None, "constellation_density")):
+            if other:
+                raise ValueError(f"soft_bins with {name}: the receiver with both records is not built")
+
     def _run(self, link=None) -> Dict[str, Any]:
         """run(); ``link`` (run_sweep): a callable (make_engine, n_sym, seed, valid_bits) -> LinkStats
         standing in for this simulation's own engine run."""
@@ -444,6 +479,10 @@ class Simulation:
             self._check_frames()
         if self.constellation_density is not None:
             self._check_density()
+        if self.soft_bins is not None:
+            self._check_soft()
+        elif self.soft_extent is not None or self.soft_weights is not None:
+            raise ValueError("soft_extent / soft_weights without soft_bins")
         sp = SerialToParallelConverter()
         noise_model = self.NOISE_SCHEME_MAPPERS.get(self.noise_scheme, AWGNoiseModel)()
         h_raw = np.asarray(DEFAULT_CHANNEL if self.channel_impulse_response is None
@@ -563,6 +602,8 @@ class Simulation:
             raise ValueError("frame_symbols needs the fused path (channel order and prefix within n_fft)")
         if not fused and self.constellation_density is not None:  # (_check_density saw the strategy classes)
             raise ValueError("constellation_density needs the fused path (channel order and prefix within n_fft)")
+        if not fused and self.soft_bins is not None:  # (_check_soft saw the strategy classes)
+            raise ValueError("soft_bins needs the fused path (channel order and prefix within n_fft)")
         if not fused and self.papr_ccdf:
             raise ValueError("papr_ccdf needs the built-in modulators, prefixes and constellations")
         if not fused and self.clip_db is not None:
@@ -597,7 +638,10 @@ class Simulation:
                              **({} if self.frame_symbols is None else {"frame_symbols": self.frame_symbols}),
                              **({} if self.constellation_density is None else {
                                  "density": self.constellation_density,
-                                 "density_extent": self.constellation_density_extent}))
+                                 "density_extent": self.constellation_density_extent}),
+                             **({} if self.soft_bins is None else {
+                                 "soft": self.soft_bins, "soft_extent": self.soft_extent,
+                                 "soft_weights": self.soft_weights}))
             if self.papr_ccdf:
                 # the per-symbol PAPR distribution of the stream just transmitted: the same plan, seed
                 # and (reference mode) the run's own bits
@@ -650,6 +694,17 @@ class Simulation:
                 "counts": d.counts.tolist(),
                 "outside": d.outside,
                 "num_points": d.n_points,
+            }
+        if self.soft_bins is not None:
+            sd = st.soft
+            results["soft_decisions"] = {
+                "bins": sd.bins,
+                "extent": sd.extent,
+                "counts": sd.counts.tolist(),
+                "invalid": sd.invalid,
+                "num_bits": sd.n_bits,
+                "gmi_bits_per_subcarrier": sd.gmi(),
+                "gmi_scale": {str(b): sd.gmi_scale(b) for b in sd.orders},
             }
         if self.clip_db is not None:
             results.update({
